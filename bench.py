@@ -8,11 +8,17 @@ per GPU.  One process per GPU; the batch shards across ranks with no data-path c
 (weak scaling); RCCL is used only for the barrier, the MAX over rank times and the 2-float
 checksum all-reduce.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg3] [--mode dropin|fused]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg3] [--mode dropin|fused] [--full]
+                    [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line (contract in the task statement) with two extra objects:
+A plain run sets up, warms up, times exactly K steps in one window and prints the headline line.  --dump-outputs DIR
+also writes the arrays the last timed step produced as DIR/<name>.npy (float32; see dump_outputs).  Everything else the
+benchmark measures moves behind --full: repeated windows when K < 200, the side configurations, the roofline and
+per-kernel figures, the CPU baselines, the parity check against the oracle, the end-to-end and EPE legs.
+
+With --full, rank 0 prints ONE JSON line (contract in the task statement) with, among others, two extra objects:
   roofline      dominant kernel (the level-2 correlation launch): algorithmic bytes
                 / mean launch duration from HIP events on the kernel's own stream
                 (hipExtLaunchKernelGGL start/stop events), against 8 TB/s HBM.
@@ -68,6 +74,13 @@ def parse():
                     help="MODULE:FACTORY of a HotPathWorkload buffers object instead of the torch-ROCm device buffers -- "
                          "the CPU test-suite runs the launcher with numpy buffers over the emulated kernels "
                          "(tests/test_bench_launcher.py); such a line is marked as a dry run, never a measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: repeated windows when --steps < 200 (median reported), the side "
+                         "configurations, rooflines, per-kernel and per-operator figures, CPU baselines, parity vs the oracle, "
+                         "end-to-end and EPE legs.  Off: set up, warm up, time --steps steps once, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32, at most "
+                         "64 MB in all: a fixed, seeded sample of each array when the whole set is larger)")
     return ap.parse_args()
 
 
@@ -696,6 +709,32 @@ def end_to_end(N, H, W, device, torch, steps=30, full=False, ref_flow=None):
             "note": "not the headline: `value` above is the matching hot path BASELINE.json's north_star names", "_flow": net_flow}
 
 
+DUMP_DATA_BYTES = 60 << 20   # array data of --dump-outputs; the .npy headers stay far inside the 64 MB the option promises
+
+
+def dump_outputs(wl, outdir, seed=20261016):
+    """Write the arrays a caller of the timed pass receives (wl.output_names(), the last step's values) as outdir/<name>.npy,
+    float32.  When they hold more than DUMP_DATA_BYTES together, every array keeps the same fraction of its elements: a
+    seeded choice of flat indices in ascending order, which depends only on the array's name order and size, so two builds
+    dump the same positions.  Returns a short record for the result line."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    names, outs = wl.output_names(), wl.outputs()
+    sizes = [int(np.prod(tuple(o.shape))) for o in outs]
+    frac = min(1.0, DUMP_DATA_BYTES / max(4 * sum(sizes), 1))
+    written = 0
+    for i, (name, o, n) in enumerate(zip(names, outs, sizes)):
+        a = o.detach().cpu().numpy() if hasattr(o, "detach") else np.asarray(o)
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if frac < 1.0:
+            idx = np.sort(np.random.default_rng(seed + i).choice(n, size=max(1, int(n * frac)), replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(outdir, name + ".npy"), a)
+        written += a.nbytes
+    return {"dir": outdir, "arrays": len(names), "MB": round(written / 1e6, 2),
+            "sampled": ("every array cut to %.4f of its elements (seeded flat indices, ascending)" % frac) if frac < 1.0 else None}
+
+
 def make_buffers(spec):
     import importlib
     mod, _, fn = spec.partition(":")
@@ -734,6 +773,8 @@ def main():
         # the whole-network training step, batch sharded over the ranks (weak scaling: 8 pairs per GPU), gradients in four flat buckets
         if not gpu:
             sys.exit("bench.py: --config e2e_train runs on the GPU only")
+        if args.dump_outputs:
+            sys.exit("bench.py: --dump-outputs covers the hot-path passes, not --config e2e_train")
         r = end_to_end_train(8, 384, 512, "cuda:%d" % torch.cuda.current_device(), torch, steps=max(1, min(args.steps, 50)), dist=dist,
                              world=world, rank=rank, barrier_timing=True)
         if rank == 0:
@@ -785,16 +826,20 @@ def main():
         wls[i % len(wls)].step(dist, wl.N * world)
     for w in wls:
         w.synchronize()
-    # K steps between barrier + synchronize on both sides, MAX over ranks (the contract).  A short window -- the driver's 20 steps are
-    # 2.7 ms -- is at the mercy of one host hiccup, so windows of fewer than 200 steps are REPEATED (every one bracketed the same way,
-    # the same count on every rank) and the line reports the median window; `windows` has the spread.
-    nwin = 1 if (args.steps >= 200 or not gpu) else max(25, min(101, int(0.1 / max(args.steps * 1.4e-4, 1e-6)) | 1))
+    # K steps between barrier + synchronize on both sides, MAX over ranks (the contract).  A plain run times exactly one such window.
+    # With --full, a short window -- the driver's 20 steps are 2.7 ms -- is at the mercy of one host hiccup, so windows of fewer than
+    # 200 steps are REPEATED (every one bracketed the same way, the same count on every rank) and the line reports the median window;
+    # `windows` has the spread.
+    nwin = 1 if (not args.full or args.steps >= 200 or not gpu) else max(25, min(101, int(0.1 / max(args.steps * 1.4e-4, 1e-6)) | 1))
     win = []
     for _ in range(nwin):
         d_ = timed_steps(wls, args.steps, dist, torch, gpu)
         win.append((d_, list(timed_steps.last_rank_seconds)))
     win.sort(key=lambda x: x[0])
     dt, rank_seconds = win[len(win) // 2]
+    dumped = None
+    if args.dump_outputs and rank == 0:   # the workload the last timed step ran on, before any other leg touches its buffers
+        dumped = dump_outputs(wls[(args.steps - 1) % len(wls)] if args.steps > 0 else wl, args.dump_outputs)
 
     # 2-float record all-reduced over RCCL (the only collective: SURVEY.md 8e)
     local_ck = wl.checksum()
@@ -878,7 +923,10 @@ def main():
     coll["per_rank_pairs_per_s"] = {"min": round(min(rates), 2), "max": round(max(rates), 2), "n": len(rates)} if rates else None
     coll["shard_seeds"] = "rank r draws its per-GPU batch from seed 20260925 + 1000 r" if gpu else "seed 20260925 + r"
     res["distributed"] = coll
-    if gpu and len(wls) == 1 and world == 1 and not args.no_graph:
+    if dumped:
+        res["outputs_dumped"] = dumped
+    full = gpu and args.full   # every leg below measures or checks something beyond the headline
+    if full and len(wls) == 1 and world == 1 and not args.no_graph:
         try:  # informational: the same pass with 3 independent batches in flight (3 streams, own outputs each)
             extra = [workload().capture() for _ in range(2)]
             pw = [wl] + extra
@@ -893,7 +941,7 @@ def main():
             del extra, pw
         except Exception as e:
             res["pipelined"] = {"error": repr(e)}
-    if gpu and len(wls) == 1 and world == 1 and not args.no_graph and args.flow == "smooth":
+    if full and len(wls) == 1 and world == 1 and not args.no_graph and args.flow == "smooth":
         try:  # what SURVEY.md 8(d)'s flow distribution costs: the same pass over a batch with i.i.d. rough flows
             rw = workload("rough").capture()
             for _ in range(50):
@@ -913,7 +961,7 @@ def main():
             del rw
         except Exception as e:
             res["rough_flow"] = {"error": repr(e)}
-    if gpu and len(wls) == 1 and world == 1 and not args.no_graph and not args.repack and args.flow == "smooth" and wl.kind in ("S", "full"):
+    if full and len(wls) == 1 and world == 1 and not args.no_graph and not args.repack and args.flow == "smooth" and wl.kind in ("S", "full"):
         try:  # what the operator's own signature costs: DeformableConvolution gets the raw filter bank on EVERY call (layer.py:117-121),
             # so a caller that cannot keep packed weights pays the re-layout kernel in front of every deformable convolution
             pw_ = hotpath.HotPathWorkload(args.config, device="cuda:%d" % torch.cuda.current_device(), mode=args.mode, prepack=False,
@@ -930,7 +978,7 @@ def main():
             del pw_
         except Exception as e:
             res["repack"] = {"error": repr(e)}
-    if gpu:
+    if full:
         try:
             res["roofline"], res["roofline_compute"] = roofline_of_dominant_kernel(wl, args.roofline_iters, torch)
             res["roofline_warp"] = warp_roofline(wl, hotpath)
@@ -939,7 +987,7 @@ def main():
         except Exception as e:  # the headline number must survive a profiler problem
             res["roofline"] = None
             res["roofline_error"] = repr(e)
-    if gpu and world == 1 and not args.no_graph and not args.no_side_configs and args.config == "cfg2" and args.mode == "dropin" \
+    if full and world == 1 and not args.no_graph and not args.no_side_configs and args.config == "cfg2" and args.mode == "dropin" \
             and args.flow == "smooth" and len(wls) == 1:
         # the other configurations north_star names, in the driver's own run: 448x1024 (configs[2]), the fused operator
         # forms on the headline batch, and the training step (configs[4]) -- 200 steps each
@@ -951,7 +999,7 @@ def main():
                 res[key] = side_config(cfg_, mode_, 200, torch, hotpath, **kw_)
             except Exception as e:
                 res[key] = {"error": repr(e)}
-    if gpu and world == 1 and not args.no_side_configs and args.config == "cfg2" and args.mode == "dropin" and args.flow == "smooth" \
+    if full and world == 1 and not args.no_side_configs and args.config == "cfg2" and args.mode == "dropin" and args.flow == "smooth" \
             and len(wls) == 1:
         try:
             wl.replay()
@@ -963,7 +1011,7 @@ def main():
             res["customop_fused"] = customop_fused_leg(wl, 200, torch, hotpath)
         except Exception as e:
             res["customop_fused"] = {"error": repr(e)}
-    if gpu and world == 1 and not args.no_side_configs and args.config == "cfg2" and args.mode == "dropin" and args.flow == "smooth" \
+    if full and world == 1 and not args.no_side_configs and args.config == "cfg2" and args.mode == "dropin" and args.flow == "smooth" \
             and not args.no_graph and not args.tuning:
         # transparency: the same pass with EVERY operator on fp32 FMA chains / the fp32 MFMA (mfn_set_arithmetic(all, MFN_ARITH_FP32)):
         # the cost volumes on corr_dma_kernel (level 2: the Gram band on v_mfma_f32_16x16x4_f32, raw operands), the deformable convolutions on dc_lds_kernel (v_mfma_f32_32x32x2_f32) -- rounds 1-3's
@@ -979,7 +1027,7 @@ def main():
             res["fp32_arithmetic"] = {"error": repr(e)}
         finally:
             _lg.set_arithmetic(all=_lg.ARITH_DEFAULT)
-    if not args.no_cpu_baseline and world == 1 and gpu:  # rank 0 at N=1 only: other ranks would idle in the barrier meanwhile
+    if full and not args.no_cpu_baseline and world == 1:  # rank 0 at N=1 only: other ranks would idle in the barrier meanwhile
         res["cpu_baseline"], want = cpu_baseline(wl, args.cpu_seconds)
         res["speedup_vs_cpu_baseline"] = round(value / res["cpu_baseline"]["value"], 1)
         wl.replay()
@@ -989,7 +1037,7 @@ def main():
             res["cpu_baseline_multithread"] = cpu_baseline_threads(wl, min(args.cpu_seconds, 8.0), os.cpu_count() or 1)
         except Exception as e:
             res["cpu_baseline_multithread"] = {"error": repr(e)}
-    if gpu and world == 1 and not args.no_e2e and wl.kind == "S":
+    if full and world == 1 and not args.no_e2e and wl.kind == "S":
         try:
             res["e2e"] = end_to_end(wl.N, wl.H, wl.W, "cuda:%d" % torch.cuda.current_device(), torch)
             exact_flow = res["e2e"].pop("_flow", None)
@@ -1011,7 +1059,7 @@ def main():
             res["e2e_train"] = end_to_end_train(wl.N, wl.H, wl.W, "cuda:%d" % torch.cuda.current_device(), torch)
         except Exception as e:
             res["e2e_train"] = {"error": repr(e)}
-    if gpu and world == 1 and not args.no_epe and wl.kind != "train":
+    if full and world == 1 and not args.no_epe and wl.kind != "train":
         try:
             res["epe"] = network_epe_delta(wl.H, wl.W, "cuda:%d" % torch.cuda.current_device())
         except Exception as e:

@@ -1,12 +1,11 @@
 """f-3: .flo and .params IO (host side).  The .flo layout is pinned by the reference's own hard-coded header bytes
-(reader/chairs/flo.py:4: b'PIEH' + 512 + 384) and, in this container, by the reference's own readers / writer
-(reader/chairs/flo.py, reader/sintel.py Flo) imported from /root/reference; the .params reader by a byte fixture
-assembled by hand from MXNet's documented NDArray-list layout and by round trips (no MXNet, no weights here)."""
-import importlib.util
+(reader/chairs/flo.py:4: b'PIEH' + 512 + 384) and by what the reference's own readers / writer (reader/chairs/flo.py,
+reader/sintel.py Flo) did with these very files, recorded in tests/golden/reference_flo_v1.json; the .params reader by a byte
+fixture assembled by hand from MXNet's documented NDArray-list layout and by round trips (no MXNet, no weights here)."""
+import hashlib
+import json
 import os
 import struct
-import sys
-import types
 
 import numpy as np
 import pytest
@@ -63,45 +62,48 @@ def test_params_round_trip_and_prefix_stripping(tmp_path):
         mio.load_params(q)
 
 
-def _load_reference_module(relpath, name, stubs=()):
-    path = os.path.join("/root/reference", relpath)
-    if not os.path.exists(path):
-        pytest.skip("/root/reference is not present (GPU box)")
-    saved = {}
-    for st in stubs:   # import-time dependencies the readers do not need for .flo files (skimage: PNG decoding)
-        saved[st] = sys.modules.get(st)
-        sys.modules.setdefault(st, types.ModuleType(st))
-        if "." in st:
-            setattr(sys.modules[st.split(".")[0]], st.split(".")[1], sys.modules[st])
-    try:
-        spec = importlib.util.spec_from_file_location(name, path)
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-        return mod
-    finally:
-        for st, old in saved.items():
-            if old is None:
-                sys.modules.pop(st, None)
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+def _sha256(b):
+    return hashlib.sha256(b).hexdigest()
 
 
 def test_flo_against_the_references_own_readers_and_writer(tmp_path):
-    """Files written here are read by the reference's readers, and the reference's writer is read back here."""
+    """Files written here are read by the reference's readers, and the reference's writer is read back here.  The reference's
+    side was recorded once, on the files this test writes (same seeds): tests/golden/reference_flo_v1.json holds the sha256 of
+    each file the readers were given and of the array they returned, and of the file Flo.save wrote; reference_sintel_24x10.flo
+    is a whole file as Flo(24, 10).save lays it down."""
+    with open(os.path.join(GOLDEN, "reference_flo_v1.json")) as f:
+        rec = json.load(f)
     rng = np.random.default_rng(4)
-    chairs = _load_reference_module("reader/chairs/flo.py", "mfn_ref_chairs_flo")
     flow = rng.standard_normal((384, 512, 2)).astype(np.float32)           # FlyingChairs size, the only one it accepts
     p = tmp_path / "chairs.flo"
     mio.write_flo(p, flow)
-    np.testing.assert_array_equal(chairs.load(str(p)), flow)
-    sintel = _load_reference_module("reader/sintel.py", "mfn_ref_sintel", stubs=("skimage", "skimage.io"))
-    flo = sintel.Flo(1024, 436)                                              # reader/sintel.py:76, predict.py:16
-    flow = rng.standard_normal((436, 1024, 2)).astype(np.float32)
+    raw = p.read_bytes()
+    ch = rec["chairs"]
+    assert raw[:12] == bytes.fromhex(ch["header_hex"])                      # the header chairs/flo.py load() demands
+    assert _sha256(raw) == ch["file_sha256"]                                # the very bytes its load() was given ...
+    assert ch["load_shape"] == list(flow.shape) and ch["load_dtype"] == "float32"
+    assert ch["load_sha256"] == _sha256(flow.tobytes())                     # ... and returned as this flow
+    np.testing.assert_array_equal(mio.read_flo(p), flow)
+    flow = rng.standard_normal((436, 1024, 2)).astype(np.float32)           # reader/sintel.py:76 Flo(1024, 436), predict.py:16
     q = tmp_path / "sintel.flo"
     mio.write_flo(q, flow)
-    np.testing.assert_array_equal(flo.load(str(q)), flow)
-    r = tmp_path / "pred.flo"
-    flo.save(flow, str(r))                                                   # what predict.py:37 writes
-    np.testing.assert_array_equal(mio.read_flo(r), flow)
-    assert q.read_bytes() == r.read_bytes()
+    si = rec["sintel"]
+    assert _sha256(q.read_bytes()) == si["file_sha256"]
+    assert si["load_shape"] == list(flow.shape) and si["load_dtype"] == "float32"
+    assert si["load_sha256"] == _sha256(flow.tobytes())
+    assert si["save_sha256"] == si["file_sha256"]                           # what predict.py:37 writes: byte-identical to ours
+    np.testing.assert_array_equal(mio.read_flo(q), flow)
+    sm = rec["sintel_small"]
+    small = np.random.default_rng(sm["seed"]).standard_normal(tuple(sm["shape"])).astype(np.float32)
+    ref_file = os.path.join(GOLDEN, sm["file"])
+    np.testing.assert_array_equal(mio.read_flo(ref_file), small)
+    assert sm["load_sha256"] == _sha256(small.tobytes())
+    r = tmp_path / "small.flo"
+    mio.write_flo(r, small)
+    assert r.read_bytes() == open(ref_file, "rb").read()
 
 
 def test_params_reader_against_hand_assembled_bytes():

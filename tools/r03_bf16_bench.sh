@@ -4,8 +4,8 @@ export TMPDIR=/tmp
 O=gpurun_out/${1:-bf16b}
 mkdir -p $O
 for r in 1 2 3; do
-  python bench.py --no-side-configs --no-e2e --no-epe --no-cpu-baseline > $O/fp32_$r.log 2> $O/err.txt
-  python bench.py --tuning dc_mma=1 --no-side-configs --no-e2e --no-epe --no-cpu-baseline > $O/bf16_$r.log 2>> $O/err.txt
+  python bench.py --full --no-side-configs --no-e2e --no-epe --no-cpu-baseline > $O/fp32_$r.log 2> $O/err.txt
+  python bench.py --full --tuning dc_mma=1 --no-side-configs --no-e2e --no-epe --no-cpu-baseline > $O/bf16_$r.log 2>> $O/err.txt
 done
 python - "$O" <<'PY'
 import json, sys, glob

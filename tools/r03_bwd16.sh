@@ -9,7 +9,7 @@ tail -2 $O/pytest_bwd.log
 timeout 300 python tools/phase_bwd_pix.py > $O/phases.txt 2>&1; grep "^L. gx=write goffset=write" $O/phases.txt
 timeout 300 python tools/phase_bwd_pix.py detail > $O/phases_detail.txt 2>&1; grep "^L. gx=write goffset=write" $O/phases_detail.txt
 timeout 300 python tools/bwd_levels.py > $O/bwd_levels.txt 2>&1; grep "^L" $O/bwd_levels.txt
-python bench.py --config cfg5 --no-epe --no-e2e --no-side-configs > $O/bench_cfg5.log 2> $O/bench_cfg5.err
+python bench.py --full --config cfg5 --no-epe --no-e2e --no-side-configs > $O/bench_cfg5.log 2> $O/bench_cfg5.err
 python - "$O" <<'PY'
 import json, sys
 j = json.loads(open(sys.argv[1] + "/bench_cfg5.log").read().strip().splitlines()[-1])

@@ -8,7 +8,7 @@ timeout 600 python -m pytest tests/test_gpu_parity.py -q -m gpu -k "corr or hot_
 tail -5 $O/pytest_corr.log
 timeout 300 python tools/corr_ab.py "corr_variant=16;corr_variant=17" 2 cfg2 7 > $O/corr_ab_l2.txt 2>&1
 tail -12 $O/corr_ab_l2.txt
-python bench.py --no-side-configs --no-e2e --no-epe > $O/bench.log 2> $O/bench.err
+python bench.py --full --no-side-configs --no-e2e --no-epe > $O/bench.log 2> $O/bench.err
 python - "$O" <<'PY'
 import json, sys
 j = json.loads(open(sys.argv[1] + "/bench.log").read().strip().splitlines()[-1])

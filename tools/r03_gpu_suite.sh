@@ -6,7 +6,7 @@ O=gpurun_out/${1:-suite}
 mkdir -p $O
 timeout 900 python -m pytest tests -q -m gpu > $O/pytest_gpu.log 2>&1
 tail -12 $O/pytest_gpu.log
-python bench.py > $O/bench.log 2> $O/bench.err
+python bench.py --full > $O/bench.log 2> $O/bench.err
 python - "$O" <<'PY'
 import json, sys
 j = json.loads(open(sys.argv[1] + "/bench.log").read().strip().splitlines()[-1])

@@ -12,7 +12,7 @@ grep "corr L" $O/corr_ab_l2.txt
 timeout 400 python tools/corr_ab.py "corr_variant=16;corr_variant=40;corr_variant=40,corr_rows=6;corr_variant=40,store_policy=2" 2 cfg3 7 > $O/corr_ab_l2_cfg3.txt 2>&1
 grep "corr L" $O/corr_ab_l2_cfg3.txt
 [ "$2" = "quick" ] && exit 0
-timeout 600 python bench.py --no-side-configs --no-e2e --no-epe --tuning corr_variant=40 > $O/bench_v40.log 2> $O/bench_v40.err
+timeout 600 python bench.py --full --no-side-configs --no-e2e --no-epe --tuning corr_variant=40 > $O/bench_v40.log 2> $O/bench_v40.err
 python - "$O" <<'PY'
 import json, sys
 try:

@@ -12,7 +12,7 @@ for lvl in 5 4 3 2; do
 timeout 300 python tools/corr_ab.py ";dc_mma=1" $lvl cfg2 5 deform >> $O/ab.txt 2>&1
 done
 grep "^deform" $O/ab.txt
-timeout 300 python bench.py --no-cpu-baseline --no-epe --no-e2e --no-side-configs --tuning dc_mma=1 --steps 300 > $O/bench_mma.log 2>&1
+timeout 300 python bench.py --full --no-cpu-baseline --no-epe --no-e2e --no-side-configs --tuning dc_mma=1 --steps 300 > $O/bench_mma.log 2>&1
 python - <<'PY'
 import json,sys
 l=[x for x in open(sys.argv[1] if len(sys.argv)>1 else 'gpurun_out/r04_dcmma/bench_mma.log') if x.startswith('{')]

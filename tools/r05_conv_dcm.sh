@@ -7,5 +7,5 @@ echo "== conv.dcm=1 (conv_mfma_kernel) =="
 timeout 300 python tools/conv_time.py 8 conv_dcm=1 2>&1 | grep -v amdgpu.ids | tail -24
 echo "== plan =="
 timeout 300 python tools/conv_time.py 8 2>&1 | grep -v amdgpu.ids | tail -24
-timeout 300 python bench.py --steps 50 --warmup 10 --no-cpu-baseline --no-epe --no-side-configs 2>&1 | tail -1 | python -c "
+timeout 300 python bench.py --full --steps 50 --warmup 10 --no-cpu-baseline --no-epe --no-side-configs 2>&1 | tail -1 | python -c "
 import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], {k:(v.get('value') if isinstance(v,dict) else v) for k,v in d.items() if k in ('e2e','e2e_fp32','e2e_full','e2e_train')}, d.get('e2e'))"

@@ -13,7 +13,7 @@ timeout 300 python tools/corr_ab.py "dc_mma=0;;dc_mt=2,dc_pt=3,dc_nw=12;dc_mt=2,
 timeout 300 python tools/corr_ab.py "dc_mma=0;;dc_mt=1,dc_pt=3,dc_nw=6;dc_mt=3,dc_pt=1,dc_nw=6;dc_mt=1,dc_pt=1,dc_nw=2;dc_mt=1,dc_pt=4,dc_nw=4;dc_mt=1,dc_pt=1,dc_nw=1" 4 cfg2 5 deform >> $O/ab.txt 2>&1
 timeout 300 python tools/corr_ab.py "dc_mma=0;;dc_mt=1,dc_pt=1,dc_nw=8;dc_mt=1,dc_pt=1,dc_nw=4;dc_mt=2,dc_pt=1,dc_nw=4;dc_mt=1,dc_pt=3,dc_nw=6;dc_mt=1,dc_pt=4,dc_nw=4;dc_mt=1,dc_pt=1,dc_nw=2" 5 cfg2 5 deform >> $O/ab.txt 2>&1
 grep "^deform" $O/ab.txt
-timeout 300 python bench.py --no-cpu-baseline --no-epe --no-e2e --no-side-configs --steps 300 > $O/bench.log 2>&1
+timeout 300 python bench.py --full --no-cpu-baseline --no-epe --no-e2e --no-side-configs --steps 300 > $O/bench.log 2>&1
 python - $O/bench.log <<'PY'
 import json,sys
 l=[x for x in open(sys.argv[1]) if x.startswith('{')]

@@ -9,15 +9,15 @@ rm -rf $G/prof_bench $G/prof_cfg5 $G/pmc_FETCH_SIZE $G/pmc_WRITE_SIZE
 rm -f $G/bench*.log
 mkdir -p $G/r05p
 if [ -z "$SKIP_BENCH" ]; then
-python bench.py > $G/bench.log 2> $G/bench.err
-python bench.py --mode fused --no-side-configs --no-e2e --no-epe --no-cpu-baseline > $G/bench_fused.log 2>> $G/bench.err
-python bench.py --config cfg3 --no-side-configs --no-e2e --no-epe --no-cpu-baseline > $G/bench_cfg3.log 2>> $G/bench.err
-python bench.py --config cfg5 --no-side-configs --no-e2e --no-epe --no-cpu-baseline > $G/bench_cfg5.log 2>> $G/bench.err
-python bench.py --config cfg4 --no-side-configs --no-e2e --no-epe --no-cpu-baseline > $G/bench_cfg4.log 2>> $G/bench.err
-python bench.py --flow rough --no-side-configs --no-e2e --no-epe --no-cpu-baseline > $G/bench_rough.log 2>> $G/bench.err
+python bench.py --full > $G/bench.log 2> $G/bench.err
+python bench.py --full --mode fused --no-side-configs --no-e2e --no-epe --no-cpu-baseline > $G/bench_fused.log 2>> $G/bench.err
+python bench.py --full --config cfg3 --no-side-configs --no-e2e --no-epe --no-cpu-baseline > $G/bench_cfg3.log 2>> $G/bench.err
+python bench.py --full --config cfg5 --no-side-configs --no-e2e --no-epe --no-cpu-baseline > $G/bench_cfg5.log 2>> $G/bench.err
+python bench.py --full --config cfg4 --no-side-configs --no-e2e --no-epe --no-cpu-baseline > $G/bench_cfg4.log 2>> $G/bench.err
+python bench.py --full --flow rough --no-side-configs --no-e2e --no-epe --no-cpu-baseline > $G/bench_rough.log 2>> $G/bench.err
 fi
-timeout 600 rocprofv3 --kernel-trace --stats -d $G/prof_bench -o bench -- python bench.py --steps 50 --warmup 10 --no-cpu-baseline --no-epe --no-side-configs --no-e2e > $G/r05p/prof_bench.log 2>&1
-timeout 300 rocprofv3 --kernel-trace --stats -d $G/prof_cfg5 -o cfg5 -- python bench.py --config cfg5 --steps 50 --warmup 10 --no-cpu-baseline --no-epe --no-e2e --no-side-configs > $G/r05p/prof_cfg5.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats -d $G/prof_bench -o bench -- python bench.py --full --steps 50 --warmup 10 --no-cpu-baseline --no-epe --no-side-configs --no-e2e > $G/r05p/prof_bench.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --stats -d $G/prof_cfg5 -o cfg5 -- python bench.py --full --config cfg5 --steps 50 --warmup 10 --no-cpu-baseline --no-epe --no-e2e --no-side-configs > $G/r05p/prof_cfg5.log 2>&1
 [ -z "$SKIP_PMC" ] && : > $G/r05p/dc_pmc.txt
 [ -n "$SKIP_PMC" ] && LEVELS="" || LEVELS="2 3 4 5"
 for lvl in $LEVELS; do
