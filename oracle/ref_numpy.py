@@ -143,3 +143,170 @@ def upsample(img, factor):
             out[:, :, a::f, b::f] = ((1 - wy) * (1 - wx) * p[:, :, :H, :W] + (1 - wy) * wx * p[:, :, :H, 1:W + 1]
                                      + wy * (1 - wx) * p[:, :, 1:H + 1, :W] + wy * wx * p[:, :, 1:H + 1, 1:W + 1])
     return out
+
+
+# ---- magnitude bounds of the backward pass ---------------------------------------------------------------------------------
+# M: per gradient element, the sum of the absolute values of the terms that element is made of (the C oracle's terms, under its
+# border rules).  |exact - computed| <= (terms) * eps * M for any summation order, so |got - want64| / M is the error a kernel
+# makes per element, whatever that element's own magnitude.  A bilinear derivative (b - a) * coef is taken as |coef||a| + |coef||b|.
+def correlation_backward_bound(gout, f1, f2, max_displacement=4):
+    """M of CorrelationBackward (kernel 1, strides 1, pad = md, multiply): (M1, M2) for (g1, g2)."""
+    ga = np.abs(np.asarray(gout, np.float64))
+    a1 = np.abs(np.asarray(f1, np.float64))
+    a2 = np.abs(np.asarray(f2, np.float64))
+    N, C, H, W = a1.shape
+    md = max_displacement
+    D = 2 * md + 1
+    a2p = np.zeros((N, C, H + 2 * md, W + 2 * md))
+    a2p[:, :, md:md + H, md:md + W] = a2
+    m1 = np.zeros((N, C, H, W))
+    m2p = np.zeros((N, C, H + 2 * md, W + 2 * md))
+    for iy in range(D):
+        for ix in range(D):
+            g = ga[:, iy * D + ix][:, None]
+            m1 += g * a2p[:, :, iy:iy + H, ix:ix + W]
+            m2p[:, :, iy:iy + H, ix:ix + W] += g * a1
+    return m1 / C, m2p[:, :, md:md + H, md:md + W] / C
+
+
+def _dc_corners(hy, wx, H, W):
+    """The C oracle's sampling rule at (hy, wx): valid mask, clamped corner rows / columns, fractions (0 where clamped)."""
+    valid = (hy >= 0) & (wx >= 0) & (hy < H) & (wx < W)
+    hs = np.where(valid, hy, 0.0)
+    ws = np.where(valid, wx, 0.0)
+    hl = np.floor(hs).astype(np.int64)
+    wl = np.floor(ws).astype(np.int64)
+    top, lef = hl >= H - 1, wl >= W - 1
+    hl, wl = np.where(top, H - 1, hl), np.where(lef, W - 1, wl)
+    hh, wh = np.where(top, H - 1, hl + 1), np.where(lef, W - 1, wl + 1)
+    lh, lw = np.where(top, 0.0, hs - hl), np.where(lef, 0.0, ws - wl)
+    return valid, hl, hh, wl, wh, lh, lw
+
+
+def deformable_convolution_backward_bound(gout, x, offset, weight, kernel=(3, 3), pad=(1, 1)):
+    """M of DeformableConvolution's backward (stride 1, dilation 1, one group, one deformable group): (Mgx, Mgoffset, Mgw, Mgbias).
+    Column gradient M: |W|^T |gout|; gx: its scatter with the bilinear weights; goffset: times the derivative's corner terms;
+    gw: |gout| . columns of |x|; gbias: sum |gout|."""
+    import scipy.sparse as sp
+    ga = np.abs(np.asarray(gout, np.float64))
+    xa = np.abs(np.asarray(x, np.float64))
+    off = np.asarray(offset, np.float64)
+    wa = np.abs(np.asarray(weight, np.float64))
+    N, Cin, H, W = xa.shape
+    Cout = wa.shape[0]
+    kh, kw = kernel
+    ph, pw = pad
+    K = kh * kw
+    Ho, Wo = H + 2 * ph - kh + 1, W + 2 * pw - kw + 1
+    P = Ho * Wo
+    assert wa.shape == (Cout, Cin, kh, kw) and off.shape == (N, 2 * K, Ho, Wo) and ga.shape == (N, Cout, Ho, Wo)
+    ys, xs = np.meshgrid(np.arange(Ho, dtype=np.float64), np.arange(Wo, dtype=np.float64), indexing="ij")
+    wt = wa.reshape(Cout, Cin * K).T                                   # (Cin*K, Cout)
+    mgx = np.zeros((N, Cin, H * W))
+    mgoff = np.zeros((N, 2 * K, P))
+    mgw = np.zeros((Cin, K, Cout))
+    for n in range(N):
+        g = ga[n].reshape(Cout, P)
+        mcol = (wt @ g).reshape(Cin, K, P)
+        xn = xa[n].reshape(Cin, H * W)
+        rows, cols, vals = [], [], []
+        for k in range(K):
+            i, j = divmod(k, kw)
+            hy = (ys - ph + i + off[n, 2 * k]).ravel()
+            wx = (xs - pw + j + off[n, 2 * k + 1]).ravel()
+            valid, hl, hh, wl, wh, lh, lw = _dc_corners(hy, wx, H, W)
+            v = valid.astype(np.float64)
+            a, b, c, d = xn[:, hl * W + wl], xn[:, hl * W + wh], xn[:, hh * W + wl], xn[:, hh * W + wh]
+            cw = ((1 - lh) * (1 - lw) * v, (1 - lh) * lw * v, lh * (1 - lw) * v, lh * lw * v)
+            colabs = cw[0] * a + cw[1] * b + cw[2] * c + cw[3] * d        # (Cin, P): columns of |x|
+            mgw[:, k] += colabs @ g.T
+            dh = ((1 - lw) * (a + c) + lw * (b + d)) * v                 # d/dh: (1-lw)(c - a) + lw (d - b)
+            dw = ((1 - lh) * (a + b) + lh * (c + d)) * v                 # d/dw: (1-lh)(b - a) + lh (d - c)
+            mgoff[n, 2 * k] = (mcol[:, k] * dh).sum(axis=0)
+            mgoff[n, 2 * k + 1] = (mcol[:, k] * dw).sum(axis=0)
+            for idx, wgt in zip((hl * W + wl, hl * W + wh, hh * W + wl, hh * W + wh), cw):
+                rows.append(idx)
+                cols.append(k * P + np.arange(P))
+                vals.append(wgt)
+        A = sp.csr_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=(H * W, K * P))
+        mgx[n] = (A @ mcol.reshape(Cin, K * P).T).T
+    mgb = ga.sum(axis=(0, 2, 3))
+    return (mgx.reshape(N, Cin, H, W), mgoff.reshape(N, 2 * K, Ho, Wo),
+            mgw.transpose(2, 0, 1).reshape(Cout, Cin, kh, kw), mgb)
+
+
+def deformable_convolution_shared_backward_bound(gout, x, flow_yx, scale, stride, weight, kernel=(3, 3), pad=(1, 1)):
+    """M of the flow-mode backward: offsets = repeat(flow * scale / stride) over the taps, d/dflow = scale / stride * sum over
+    the taps of d/doffset; (Mgx, Mgflow, Mgw, Mgbias)."""
+    K = kernel[0] * kernel[1]
+    fl = np.asarray(flow_yx, np.float32)
+    off = np.repeat((fl * np.float32(scale) / np.float32(stride))[:, None], K, axis=1).reshape(fl.shape[0], 2 * K, *fl.shape[2:])
+    mgx, mgoff, mgw, mgb = deformable_convolution_backward_bound(gout, x, off, weight, kernel, pad)
+    N, _, H, W = mgoff.shape
+    return mgx, mgoff.reshape(N, K, 2, H, W).sum(axis=1) * (abs(float(scale)) / abs(float(stride))), mgw, mgb
+
+
+def warp_positions(flow_yx, clip_grid=False, dtype=np.float64):
+    """The sample positions of Reconstruction2D[Smooth] as GridGenerator('warp') + BilinearSampler form them, in `dtype`:
+    grid = (flow + index) / ((size-1)/2) - 1 [clipped], real = (grid + 1) * (size-1) / 2.  Returns (y_real, x_real, y_in, x_in):
+    y_in / x_in say where the unclipped grid lies inside [-1, 1] (the clip's gradient mask)."""
+    fl = np.asarray(flow_yx, dtype)
+    N, _, H, W = fl.shape
+    t = np.dtype(dtype).type
+    nx, ny = t((W - 1) / 2.0), t((H - 1) / 2.0)
+    ys, xs = np.meshgrid(np.arange(H).astype(dtype), np.arange(W).astype(dtype), indexing="ij")
+    gxr = (fl[:, 1] + xs) / nx - t(1)
+    gyr = (fl[:, 0] + ys) / ny - t(1)
+    gxc, gyc = (np.clip(gxr, t(-1), t(1)), np.clip(gyr, t(-1), t(1))) if clip_grid else (gxr, gyr)
+    yr = (gyc + t(1)) * t(H - 1) / t(2)
+    xr = (gxc + t(1)) * t(W - 1) / t(2)
+    one = np.ones_like(gxr, dtype=bool)
+    y_in = (gyr >= -1) & (gyr <= 1) if clip_grid else one
+    x_in = (gxr >= -1) & (gxr <= 1) if clip_grid else one
+    return (yr.astype(np.float64), xr.astype(np.float64), y_in, x_in)
+
+
+def warp_backward_at(gout, x, positions, bound=False):
+    """fp64 BilinearSampler backward at given sample positions (warp_positions), composed with GridGenerator('warp')'s backward:
+    (gx, gflow).  bound=True: the magnitude bound M instead -- |gout| times the bilinear weights for gx; for gflow the terms of
+    the derivative as MXNet's sampler (and warp_bwd_kernel) forms it, -(tr - br + (tl - tr - bl + br) * wx) for d/dy, each as
+    |coef| |value| (the form is exact, but rounds at the scale of all four corners); d/dflow is zero where the clip cuts the grid."""
+    g_all = np.asarray(gout, np.float64)
+    x_all = np.asarray(x, np.float64)
+    if bound:
+        g_all, x_all = np.abs(g_all), np.abs(x_all)
+    yr_all, xr_all, yin_all, xin_all = positions
+    N, C, H, W = x_all.shape
+    gx = np.zeros((N, C, H * W))
+    gf = np.zeros((N, 2, H, W))
+    for n in range(N):
+        yr, xr = yr_all[n].ravel(), xr_all[n].ravel()
+        y0 = np.floor(yr).astype(np.int64)
+        x0 = np.floor(xr).astype(np.int64)
+        wy = 1.0 - (yr - y0)
+        wx = 1.0 - (xr - x0)
+        g = g_all[n].reshape(C, H * W)
+        xn = x_all[n].reshape(C, H * W)
+        vals = []
+        for dy, dx, wgt in ((0, 0, wy * wx), (0, 1, wy * (1 - wx)), (1, 0, (1 - wy) * wx), (1, 1, (1 - wy) * (1 - wx))):
+            yy, xx = y0 + dy, x0 + dx
+            ok = (yy >= 0) & (yy <= H - 1) & (xx >= 0) & (xx <= W - 1)
+            idx = np.where(ok, yy * W + xx, 0)
+            np.add.at(gx[n], (slice(None), idx[ok]), g[:, ok] * wgt[ok])
+            vals.append(np.where(ok, xn[:, idx], 0.0))
+        tl, tr, bl, br = vals
+        if bound:   # the terms of BilinearSampler's own form, tr - br + (tl - tr - bl + br) * wx (it cancels tr, br as wx -> 1)
+            d_y = tr + br + wx * (tl + tr + bl + br)
+            d_x = bl + br + wy * (tl + tr + bl + br)
+        else:
+            d_y = wx * (bl - tl) + (1 - wx) * (br - tr)
+            d_x = wy * (tr - tl) + (1 - wy) * (br - bl)
+        gf[n, 0] = np.where(yin_all[n], (g * d_y).sum(axis=0).reshape(H, W), 0.0)
+        gf[n, 1] = np.where(xin_all[n], (g * d_x).sum(axis=0).reshape(H, W), 0.0)
+    return gx.reshape(N, C, H, W), gf
+
+
+def warp_backward_bound(gout, x, flow_yx, clip_grid=False, positions_dtype=np.float64):
+    """M of Reconstruction2D[Smooth]'s backward: (Mgx, Mgflow), at the sample positions the grid arithmetic gives in
+    `positions_dtype` (float64: the fp64 oracle's; float32: the fp32 kernels' and the fp32 oracle's)."""
+    return warp_backward_at(gout, x, warp_positions(flow_yx, clip_grid, positions_dtype), bound=True)

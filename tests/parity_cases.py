@@ -551,3 +551,55 @@ def case_leaky_corr_backward(ops, oracle, to_dev, to_host, shape, md=4, seed=0):
     w1, w2 = oracle.correlation_backward(gpre_ref, f1, f2, kernel_size=1, max_displacement=md, stride1=1, stride2=1, pad_size=md)
     check_close(to_host(g1), w1, tol=2e-5, what="leaky corr g1 %s" % (shape,))
     check_close(to_host(g2), w2, tol=2e-5, what="leaky corr g2 %s" % (shape,))
+
+
+# ---- fp64 acceptance of the backward pass (tests/test_backward_fp64.py) --------------------------------------------------------
+def assert_magnitude_bound(M, want64, what=""):
+    """M (oracle/ref_numpy.*_bound) bounds the fp64 result element by element (up to 1e-12 of M: the oracle's own fp64 rounding)
+    and is zero only where the result is."""
+    M, want64 = np.asarray(M, np.float64), np.asarray(want64, np.float64)
+    assert M.shape == want64.shape, (M.shape, want64.shape)
+    assert (M >= 0).all() and np.isfinite(M).all(), what
+    over = np.abs(want64) - M * (1 + 1e-12)
+    assert (over <= 0).all(), "%s: |want64| > M at %d elements (worst %.3e)" % (what, int((over > 0).sum()), over.max())
+    assert not (want64[M == 0] != 0).any(), "%s: M == 0 where the gradient is not" % what
+
+
+def graded_gout(rng, shape):
+    """N(0,1) output gradients scaled per pixel by 10**U(-6, 0), the first image as a whole by 1e-3: training gradients span many
+    orders of magnitude, and an error in a small element is invisible to a bar scaled by the tensor's maximum."""
+    N, C, H, W = shape
+    g = rng.standard_normal(shape) * 10.0 ** rng.uniform(-6.0, 0.0, (N, 1, H, W))
+    g[0] *= 1e-3
+    return g.astype(np.float32)
+
+
+def check_fp64_bound(got, want64, ref32, M, what="", base=None):
+    """The backward acceptance rule: per element e = |got - want64| / M (M: oracle/ref_numpy.*_bound).
+      bound             max e_lib <= 4 * max e_ref32 + 16 * 2^-24 over the elements with M > 0;
+      structural zeros  where M == 0 no term exists: got is exactly 0 (exactly `base`, the caller's values, for req 'add');
+      finiteness        every output element is finite.
+    `ref32` is the fp32 oracle's gradient; with `base`, `got` holds base + gradient and the fp32 oracle's error includes the rounding
+    of that addition.  Returns (max e_lib, max e_ref32)."""
+    got = np.asarray(got, np.float64)
+    want64, ref32, M = (np.asarray(a, np.float64) for a in (want64, ref32, M))
+    assert got.shape == want64.shape == ref32.shape == M.shape, (what, got.shape, want64.shape, ref32.shape, M.shape)
+    assert np.isfinite(got).all(), "%s: %d non-finite outputs" % (what, int((~np.isfinite(got)).sum()))
+    b = np.zeros_like(got) if base is None else np.asarray(base, np.float64)
+    if base is not None:   # the fp32 oracle accumulating into the same buffer: its last rounding is that of the addition
+        ref32 = (np.asarray(base, np.float32) + ref32.astype(np.float32)).astype(np.float64) - b
+    z = M == 0
+    bad = z & (got != b)
+    assert not bad.any(), "%s: %d nonzero outputs where no term exists (first at %s, value %.3e)" % (
+        what, int(bad.sum()), np.argwhere(bad)[0].tolist(), (got - b)[bad][0])
+    nz = ~z
+    if not nz.any():
+        return 0.0, 0.0
+    e_lib = float((np.abs(got - b - want64)[nz] / M[nz]).max())
+    e_ref = float((np.abs(ref32 - want64)[nz] / M[nz]).max())
+    bar = 4.0 * e_ref + 16.0 * 2.0 ** -24
+    # the bar must be able to fail: a gradient off by 2^-12 of M in every element, or halved, lies above it
+    e_half = 0.5 * float((np.abs(want64)[nz] / M[nz]).max())
+    assert bar < 2.0 ** -12 and e_half > bar, "%s: vacuous bar %.3e (fp32 oracle %.3e, halved gradient %.3e)" % (what, bar, e_ref, e_half)
+    assert e_lib <= bar, "%s: max |got - want64| / M = %.3e > %.3e (4 x fp32 oracle's %.3e + 16 ulp)" % (what, e_lib, bar, e_ref)
+    return e_lib, e_ref

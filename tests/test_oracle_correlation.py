@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 from oracle import ref_numpy
+from tests import parity_cases as pc
 
 
 def test_out_shape(oracle):
@@ -112,3 +113,22 @@ def test_backward_matches_numeric_gradient(oracle):
             m[idx] -= eps
             num = (loss(p, f2) - loss(m, f2)) / (2 * eps) if which == 0 else (loss(f1, p) - loss(f1, m)) / (2 * eps)
             assert abs(num - g[idx]) < 1e-6
+
+
+@pytest.mark.parametrize("shape,md", [((2, 3, 5, 7), 4), ((1, 4, 9, 6), 2), ((1, 2, 1, 3), 4)])
+def test_backward_bound_covers_the_fp64_gradient(oracle, shape, md):
+    """ref_numpy.correlation_backward_bound: M >= |fp64 gradient|, zero only where the gradient is (a zero feature row, zero
+    output gradients), equal to the oracle's backward on |inputs|."""
+    rng = np.random.default_rng(17 + md)
+    f1, f2 = rng.standard_normal(shape).astype(np.float32), rng.standard_normal(shape).astype(np.float32)
+    f2[..., 0, :] = 0.0
+    D = 2 * md + 1
+    go = rng.standard_normal((shape[0], D * D) + shape[2:]).astype(np.float32)
+    go[:, :, :, -1] = 0.0
+    want = oracle.correlation_backward(go, f1, f2, max_displacement=md, pad_size=md, dtype=np.float64)
+    M = ref_numpy.correlation_backward_bound(go, f1, f2, md)
+    abs_want = oracle.correlation_backward(np.abs(go), np.abs(f1), np.abs(f2), max_displacement=md, pad_size=md, dtype=np.float64)
+    for m, r, a, nm in zip(M, want, abs_want, ("g1", "g2")):
+        pc.assert_magnitude_bound(m, r, nm)
+        np.testing.assert_allclose(m, a, rtol=1e-12, atol=1e-12 * np.abs(a).max(), err_msg=nm)
+    assert (M[0] == 0).any()

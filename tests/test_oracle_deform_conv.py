@@ -6,6 +6,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import ref_numpy
+from tests import parity_cases as pc
 
 
 def _case(seed, N=2, Cin=4, Cout=6, H=7, W=9):
@@ -159,3 +160,44 @@ def test_fraction_source_flag_a3_vs_mxnet_kernel(oracle):
     assert not np.array_equal(a, b)                                   # two different fp32 evaluations ...
     assert np.abs(a - b).max() <= 5e-6 * scale                        # ... of the same sample
     assert np.abs(a64 - b64).max() <= 1e-12 * scale                   # identical in exact arithmetic
+
+
+def _bound_offsets(rng, N, H, W):
+    """Per-tap offsets: sub-pixel noise, integers (floors on the lattice, the [H-1, H) clamp), rows in (-1, 0), far outside."""
+    off = (rng.standard_normal((N, 18, H, W)) * 1.5).astype(np.float32)
+    off[:, :, 1::3] = np.round(off[:, :, 1::3])
+    off[:, 0::2, 2, :] = np.float32(H - 1) - np.arange(H)[2] + np.float32(0.25)   # every tap of row 2 lands in [H-1, H) (tap 0) or beyond
+    off[:, 0::2, 0, 1::2] = np.float32(-0.5)                                        # rows in (-1, 0): nothing
+    off[:, :, 0, 0] = np.float32(3.0 * max(H, W))
+    off[:, 1::2, -1, -1] = np.float32(-1e6)
+    return off
+
+
+@pytest.mark.parametrize("shared", [False, True])
+def test_backward_bound_covers_the_fp64_gradient(oracle, shared):
+    """ref_numpy.deformable_convolution_backward_bound (the per-element magnitude the fp64 acceptance divides by): M >= |fp64
+    gradient|, zero only where the gradient is, and for gx / gw / gbias the oracle's own backward on |inputs|."""
+    rng = np.random.default_rng(41 + shared)
+    N, Cin, Cout, H, W = 2, 3, 4, 6, 9
+    x, w, _ = _case(7 + shared, N=N, Cin=Cin, Cout=Cout, H=H, W=W)
+    go = rng.standard_normal((N, Cout, H, W)).astype(np.float32)
+    go[1, :, :2] = 0.0
+    if shared:
+        fl = _bound_offsets(rng, N, H, W)[:, :2]
+        scale, stride = 20.0, 8.0
+        fl = (fl * np.float32(stride / scale)).astype(np.float32)
+        off = oracle.offsets_from_flow(fl, scale, stride)
+        M = ref_numpy.deformable_convolution_shared_backward_bound(go, x, fl, scale, stride, w)
+        want = list(oracle.deformable_convolution_backward(go, x, off, w, dtype=np.float64))
+        want[1] = want[1].reshape(N, 9, 2, H, W).sum(axis=1) * (scale / stride)
+    else:
+        off = _bound_offsets(rng, N, H, W)
+        M = ref_numpy.deformable_convolution_backward_bound(go, x, off, w)
+        want = oracle.deformable_convolution_backward(go, x, off, w, dtype=np.float64)
+    for m, r, nm in zip(M, want, ("gx", "goffset", "gw", "gbias")):
+        pc.assert_magnitude_bound(m, r, nm)
+    assert (M[1] == 0).any()   # the far-outside pixels: structural zeros
+    ax, aw = np.abs(x), np.abs(w)
+    abs_want = oracle.deformable_convolution_backward(np.abs(go), ax, off, aw, dtype=np.float64)
+    for k, nm in ((0, "gx"), (2, "gw"), (3, "gbias")):
+        np.testing.assert_allclose(M[k], abs_want[k], rtol=1e-12, atol=1e-12 * np.abs(abs_want[k]).max(), err_msg=nm)

@@ -6,6 +6,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import ref_numpy
+from tests import parity_cases as pc
 
 
 def _rand(shape, seed):
@@ -111,3 +112,46 @@ def test_upsample_matches_numpy(oracle):
         p = F.pad(torch.tensor(img, dtype=torch.float64).reshape(-1, 1, 5, 6), (0, 1, 0, 1), mode="replicate")
         want = F.conv_transpose2d(p, k, stride=f, padding=f - 1)[:, :, :-1, :-1].reshape(2, 2, 5 * f, 6 * f)
         np.testing.assert_allclose(got, want.numpy(), atol=1e-12)
+
+
+@pytest.mark.parametrize("clip", [False, True])
+def test_backward_bound_covers_the_fp64_gradient(oracle, clip):
+    """ref_numpy.warp_backward_bound: M >= |fp64 gradient| for gx and gflow (integer flows on the lattice, samples across the
+    borders and far outside, the clip's zero gradient), zero only where the gradient is; gx's M is the oracle's gx on |inputs|."""
+    rng = np.random.default_rng(5 + clip)
+    N, C, H, W = 2, 3, 6, 9
+    x = rng.standard_normal((N, C, H, W)).astype(np.float32)
+    fl = (rng.standard_normal((N, 2, H, W)) * 2.0).astype(np.float32)
+    fl[:, :, ::2] = np.round(fl[:, :, ::2])
+    fl[:, 0, 1, :3] = np.float32(-1.5)            # above the top border
+    fl[:, 1, 3, -2:] = np.float32(0.5)            # across the right border
+    fl[:, :, 4, 4] = np.float32(1e4)              # far outside
+    fl[:, 0, 5, 0] = np.float32(-H)
+    go = rng.standard_normal((N, C, H, W)).astype(np.float32)
+    go[1, :, 2] = 0.0
+    want = oracle.warp_backward(go, x, fl, clip_grid=clip, dtype=np.float64)
+    M = ref_numpy.warp_backward_bound(go, x, fl, clip_grid=clip)
+    pc.assert_magnitude_bound(M[0], want[0], "gx")
+    pc.assert_magnitude_bound(M[1], want[1], "gflow")
+    assert (M[1] == 0).any()
+    ax = oracle.warp_backward(np.abs(go), np.abs(x), fl, clip_grid=clip, dtype=np.float64)[0]
+    np.testing.assert_allclose(M[0], ax, rtol=1e-12, atol=1e-12 * np.abs(ax).max())
+
+
+@pytest.mark.parametrize("clip", [False, True])
+def test_backward_at_positions_is_the_fp64_oracle(oracle, clip):
+    """ref_numpy.warp_backward_at (the fp64 arbiter at given sample positions, which the acceptance tests evaluate at the fp32
+    kernels' positions) equals the C oracle's fp64 backward at the fp64 oracle's positions, element by element relative to M."""
+    rng = np.random.default_rng(9 + clip)
+    N, C, H, W = 2, 3, 7, 10
+    x = rng.standard_normal((N, C, H, W)).astype(np.float32)
+    fl = (rng.standard_normal((N, 2, H, W)) * 3.0).astype(np.float32)
+    fl[:, :, 3, 3] = np.float32(40.0)
+    go = rng.standard_normal((N, C, H, W)).astype(np.float32)
+    want = oracle.warp_backward(go, x, fl, clip_grid=clip, dtype=np.float64)
+    pos = ref_numpy.warp_positions(fl, clip)
+    got = ref_numpy.warp_backward_at(go, x, pos)
+    M = ref_numpy.warp_backward_at(go, x, pos, bound=True)
+    for g, w, m, nm in zip(got, want, M, ("gx", "gflow")):
+        assert (np.abs(g - w) <= 1e-12 * m).all(), nm
+        assert not g[m == 0].any() and not w[m == 0].any(), nm
