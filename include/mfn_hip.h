@@ -365,6 +365,8 @@ int mfn_profile_dump(char *buf, int cap);
  * (tests/test_gpu_parity.py::test_deform_numeric_range_edge_cases).
  * Layouts packed by mfn_deform_conv_pack_weights / mfn_conv2d_pack_weights depend on the arithmetic in force when they were packed;
  * a call under another arithmetic refuses them (layout tag) instead of misreading them.
+ * Like mfn_set_tuning, mfn_set_arithmetic must not race with calls in flight: a call is planned from one reading of the settings,
+ * but a size query and the run that follows it are two readings.
  * op: "correlation" | "deformable_convolution" | "convolution" | "all".  Unknown op / mode: MFN_E_PARAM. */
 #define MFN_ARITH_DEFAULT (-1)
 #define MFN_ARITH_FP32 0

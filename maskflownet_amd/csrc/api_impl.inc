@@ -50,6 +50,10 @@ Tuning g_tuning;
 struct Arith { std::atomic<int> corr{-1}, deform{-1}, conv{-1}; };
 static Arith t_arith;
 void *g_timeline = nullptr;  // measurement only (mfn_debug_set_timeline)
+// One reading of the process-wide settings.  Every exported entry point that plans takes it once (each atomic loaded once) and passes
+// it down, so that a call is planned from one set of values and every plan below is a function of its arguments.
+struct Settings { Tuning t; int corr, deform, conv; };
+static Settings settings_now() { return Settings{g_tuning, t_arith.corr.load(), t_arith.deform.load(), t_arith.conv.load()}; }
 
 // ---- correlation ---------------------------------------------------------------------------------
 static int corr_shape(int H, int W, int md, int kernel, int s1, int s2, int pad, int *tc, int *th, int *tw) {
@@ -71,10 +75,21 @@ static int corr_shape(int H, int W, int md, int kernel, int s1, int s2, int pad,
   return 0;
 }
 
+// What corr_plan (below) decides for a forward call and corr_fwd_common executes.
+struct CorrPlan {
+  CorrFamily family;
+  const CorrForm *form;   // Tiled / Dma / Gram / GramK: the template point (channel groups, row split, terms, f2 rows)
+  int D;                  // displacements per axis (every family but Generic: 9 or 5)
+  int tile_w, tile_h;     // Tiled / Dma: pixels per tile
+  int slices;             // Tiled / Dma: channel slices over blockIdx.y; > 1: partial sums in the workspace + corr_reduce
+  int rows;               // Gram: output rows per work item
+  int store_policy;
+  size_t ws_bytes;        // workspace the launch uses
+};
 template <int D>
-static int corr_dispatch_tw(const CorrParams &p, int tw, int variant, hipStream_t s) {
-  if (variant >= 8) return corr_dma_variant<D>(p, variant, s);
-  return tw == 16 ? corr_tiled_variant<D, 16>(p, variant, s) : corr_tiled_variant<D, 8>(p, variant, s);
+static int corr_tile_launch(const CorrParams &p, const CorrPlan &pl, hipStream_t s) {
+  if (pl.family == CorrFamily::Dma) return corr_dma_form<D>(p, *pl.form, s);
+  return pl.tile_w == 16 ? corr_tiled_form<D, 16>(p, s) : corr_tiled_form<D, 8>(p, s);
 }
 
 }  // namespace mfn
@@ -90,100 +105,35 @@ int MFN_API(correlation_out_shape)(int H, int W, int md, int kernel, int s1, int
   return corr_shape(H, W, md, kernel, s1, s2, pad, tc, th, tw);
 }
 
-// Does the plan give a 32-channel level of >= 400 tiles to corr_gram_kernel?  Same box, same session (profiles/
-// r04_corr_gram_experiments.md section 7): level 2 of 384x512 at batch 8 back to back 10.45 against 13.2 us, rocprofv3 average
-// 12.65 against 15.6 us, inside the pass 12.3-12.5 us = 0.57-0.58 of 8 TB/s against 14.2 us = 0.50; 448x1024 at batch 4 13.7
-// against 17.6 us; on buffers rotated through more than the Infinity Cache a tie (17.95 against 17.3-17.8 us).  Yes;
-// corr.gram = 0 keeps the FMA kernel.
-static bool corr_gram_default(int /*N*/, int /*H*/, int /*W*/) { return true; }
-
+// ---- correlation forward: one plan -----------------------------------------------------------------
 // Does the plan give this level to corr_gramk_kernel (the coarse levels' Gram band, channels over the waves of a block), and
 // with how many f2 rows per block?  Same box, back to back in a graph (profiles/r04_corr_gramk.txt), 384x512 at batch 8 /
 // 448x1024 at batch 4: level 6 (24 / 32 f1 blocks of 8 x 2 px) 7.85 -> 3.4 us / 7.58 -> 3.4 with two rows per block;
 // level 5 (96 / 112) 7.18 -> 3.4 / 7.17 -> 3.9; level 4 (384 / 448) 7.02 -> 5.95 / 9.13 -> 7.0 with half the window per
 // block; level 3 (1536 / 1792 blocks) loses (9.65 -> 12.0 us: every f2 row is converted by five blocks) and keeps its kernel.
-// corr.gram = 0 keeps the fp32-FMA kernels everywhere.  Returns the variant or 0.
-static int corr_gramk_plan(int N, int C, int H, int W, int D) {
-  if (t_arith.corr == 0 || (g_tuning.path_generic & 1) || C <= 32) return 0;
+// MFN_ARITH_FP32 keeps the fp32-FMA kernels everywhere.  Returns the form or nullptr.
+static const CorrForm *corr_gramk_plan(int N, int C, int H, int W, const Settings &st) {
+  if (st.corr == 0 || C <= 32 || !corr_gramk_shape_ok(C, W)) return nullptr;
   const long nb = (long)N * cdiv(H, 2) * cdiv(W, 8);
-  const int variant = nb <= 160 ? 44 : (nb <= 512 ? 45 : 0);
-  return variant && corr_gramk_shape_ok(C, W) ? variant : 0;
+  return nb <= 160 ? &kCorrForms[kCorrGramK2] : (nb <= 512 ? &kCorrForms[kCorrGramKHalf] : nullptr);
 }
 
-// slices the tiled kernel would use for this shape (0 = not the tiled path)
-static int corr_plan(int N, int C, int H, int W, int md, int kernel, int s1, int s2, int pad, int is_multiply,
-                     int *tw_out, int *variant_out) {
-  const int r = md / s2, D = 2 * r + 1;
-  const bool fast = (g_tuning.path_generic & 1) == 0 && kernel == 1 && s1 == 1 && s2 == 1 && pad == md && is_multiply &&
-                    (D == 9 || D == 5) && (W % 4 == 0);
-  if (!fast) return 0;
-  int twc = W >= 16 ? 16 : 8;   // corr_tiled_kernel only runs on images narrower than 32 columns
-  int variant = g_tuning.corr_variant;
-  const long t32 = (long)N * cdiv(W, 32) * cdiv(H, 4);   // 32x4-pixel tiles
-  const int nw = (D + 1) / 2;                             // row-pair waves of a tile
-  if (!corr_variant_known(variant) && corr_gramk_plan(N, C, H, W, D)) variant = corr_gramk_plan(N, C, H, W, D);
-  if (!corr_variant_known(variant)) {
-    // >= 400 tiles (level 2): the single-buffered LDS-DMA form (16) keeps every block of the launch resident (17.0 vs 18.6 us
-    // for the double-buffered ring at 384x512).  128-399 tiles (level 3): two channel groups per block, reduced through LDS
-    // in the same launch (9.7 us; 13.6 with one group).  Fewer tiles than that leave CUs idle and the work of one tile is
-    // what ONE CU can pull through its LDS and VALU: the displacement rows of a tile are spread over blockIdx.z (variant 26:
-    // one row pair per block and 4 channel groups; 31: two row pairs, 2 groups) as long as the launch still fits one round
-    // of 256 CUs -- level 4 (48 tiles) 12.4 -> 7.1 us, level 5 (24 half-filled tiles) 13.0 (band kernel) -> 7.2 us,
-    // 448x1024: level 4 (56 tiles) 12.7 -> 9.3, level 5 15.3 -> 7.2 us.  At 192 tiles the split loses (10.8-20 us vs 9.7).
-    if (W < 16) variant = 6;
-    else if (t32 * nw <= 256) variant = 26;
-    else if (W < 32) variant = 6;
-    else if (t32 * ((nw + 1) / 2) <= 256) variant = 31;
-    else variant = t32 >= 400 ? 16 : (t32 >= 128 ? 20 : 22);
-    // level 2 (32 channels, >= 400 tiles): the Gram band on the matrix cores where the plan says so (kCorrGramDefault, corr.gram)
-    if (variant == 16 && C == 32 && W % 8 == 0 && (t_arith.corr < 0 ? corr_gram_default(N, H, W) : t_arith.corr != 0)) variant = corr_variant_gram(g_tuning.corr_form) ? g_tuning.corr_form : 48;
-    // ... and under MFN_ARITH_FP32 the same band on the fp32 matrix instruction (form 46: raw operands, an fmaf chain over the channels
-    // in order, bitwise): 12.5 us against corr_dma_kernel's 14.0 back to back (corr.form = 16 keeps the latter)
-    else if (variant == 16 && C == 32 && W % 8 == 0 && t_arith.corr == 0 && g_tuning.corr_form != 16) variant = 46;
-    // level 3 (64 channels, 128-399 tiles): the same band with a two-chunk K loop (form 48 only; corr.form = 20 keeps corr_dma_kernel's
-    // two channel groups: 9.95 -> 8.30 us back to back at 384x512 / batch 8, 10.04 -> 8.37 at 448x1024 / batch 4, profiles/r06_corr_l3.txt)
-    if (variant == 20 && C == 64 && W % 8 == 0 && t_arith.corr != 0 && g_tuning.corr_form != 20) variant = 48;
-  }
-  if (corr_variant_gram(variant) && (C == 32 || (C == 64 && variant == 48 && W % 8 == 0)) &&
-      corr_gram_range_ok(N, H, W, corr_gram_rows(N, H, W, g_tuning.corr_rows, C))) {   // Gram band on the matrix cores: its own tiling, no channel slices
-    if (tw_out) *tw_out = 8;
-    if (variant_out) *variant_out = variant;
-    return 1;
-  }
-  if (corr_variant_gramk(variant) && corr_gramk_shape_ok(C, W)) {   // coarse levels: channels over the waves of a block
-    if (tw_out) *tw_out = 8;
-    if (variant_out) *variant_out = variant;
-    return 1;
-  }
-  if (corr_variant_gram(variant) || corr_variant_gramk(variant)) {   // asked for, but not a level that kernel takes: the plan's choice
-    if (W < 16) variant = 6;
-    else if (t32 * nw <= 256) variant = 26;
-    else if (W < 32) variant = 6;
-    else if (t32 * ((nw + 1) / 2) <= 256) variant = 31;
-    else variant = t32 >= 400 ? 16 : (t32 >= 128 ? 20 : 22);
-  }
-  if (W < 32 && !((variant == 26 || variant == 31) && W >= 16)) variant = 6;   // the 32x4-tile kernels want full-width tiles
-  else if (variant == 6) variant = 16;
-  if (variant >= 8) twc = 32;
-  const long tiles = (long)N * cdiv(W, twc) * cdiv(H, corr_variant_tile_h(twc, variant));
-  int slices = 1;  // few tiles, many channels: split channels until every CU has a block
-  if (tiles < 128 && variant < 20)  // the grouped tile kernels (20, 22) split the channels inside the block instead
-    while (tiles * slices < 256 && C / (slices * 2) >= 8 && slices < 32) slices *= 2;
-  if (slices > C / 4) slices = C / 4 > 0 ? C / 4 : 1;
-  if (tw_out) *tw_out = twc;
-  if (variant_out) *variant_out = variant;
-  return slices;
-}
-
-size_t MFN_API(correlation_workspace_bytes)(int N, int C, int H, int W, int md, int kernel, int s1, int s2, int pad,
-                                            int is_multiply) {
-  int tc, th, tw;
-  if (N <= 0 || C <= 0 || corr_shape(H, W, md, kernel, s1, s2, pad, &tc, &th, &tw)) return 0;
-  if (g_tuning.corr_direct != 2 && (long)H * W < 180 && W % 4 == 0 && g_tuning.corr_variant < 0 && kernel == 1 && s1 == 1 && s2 == 1 && pad == md && is_multiply && (md == 4 || md == 2))
-    return 0;  // direct kernel (or corr_gramk_kernel: no workspace either)
-  const int slices = corr_plan(N, C, H, W, md, kernel, s1, s2, pad, is_multiply, nullptr, nullptr);
-  if (slices <= 1) return 0;
-  return (size_t)slices * N * tc * th * tw * sizeof(float);
+// The tile kernel of a level by its count of 32x4-pixel tiles.
+// >= 400 tiles (level 2): the single-buffered LDS-DMA form (16) keeps every block of the launch resident (17.0 vs 18.6 us
+// for the double-buffered ring at 384x512).  128-399 tiles (level 3): two channel groups per block, reduced through LDS
+// in the same launch (9.7 us; 13.6 with one group).  Fewer tiles than that leave CUs idle and the work of one tile is
+// what ONE CU can pull through its LDS and VALU: the displacement rows of a tile are spread over blockIdx.z (variant 26:
+// one row pair per block and 4 channel groups; 31: two row pairs, 2 groups) as long as the launch still fits one round
+// of 256 CUs -- level 4 (48 tiles) 12.4 -> 7.1 us, level 5 (24 half-filled tiles) 13.0 (band kernel) -> 7.2 us,
+// 448x1024: level 4 (56 tiles) 12.7 -> 9.3, level 5 15.3 -> 7.2 us.  At 192 tiles the split loses (10.8-20 us vs 9.7).
+static const CorrForm *corr_tile_form(int N, int H, int W, int D) {
+  const long t32 = (long)N * cdiv(W, 32) * cdiv(H, 4);
+  const int nw = (D + 1) / 2;   // row-pair waves of a tile
+  if (W < 16) return &kCorrForms[kCorrTiled];
+  if (t32 * nw <= 256) return &kCorrForms[kCorrDmaRows1];
+  if (W < 32) return &kCorrForms[kCorrTiled];
+  if (t32 * ((nw + 1) / 2) <= 256) return &kCorrForms[kCorrDmaRows2];
+  return &kCorrForms[t32 >= 400 ? kCorrDma1 : (t32 >= 128 ? kCorrDma2 : kCorrDma3)];
 }
 
 // Cache policy of a kernel's output stores (mfn_rt.h: mfn_store4_stream), from measurements of every kernel INSIDE the
@@ -191,13 +141,93 @@ size_t MFN_API(correlation_workspace_bytes)(int N, int C, int H, int W, int md, 
 // through (level 2: 17.4 -> 15.6 us inside the pass, 17-21 -> 14.8 us back to back; level 3: 12.4 -> 11.6 us); the
 // deformable conv's output stays plain because the next kernel reads it on the same XCD; smaller outputs and the
 // latency-bound coarse levels lose a little with any policy.
-static int store_policy_for(size_t out_bytes, int preferred, int family_override, size_t below = (size_t)-1) {
+static int store_policy_for(const Settings &st, size_t out_bytes, int preferred, int family_override, size_t below = (size_t)-1) {
   if (family_override >= 0) return family_override;
-  if (g_tuning.store_policy >= 0) return g_tuning.store_policy;
+  if (st.t.store_policy >= 0) return st.t.store_policy;
   return (out_bytes >= ((size_t)4 << 20) && out_bytes < below) ? preferred : 0;
 }
 
-static int corr_fwd_common(const float *d1, const float *d2, float *out, int N, int C, int H, int W, int md, int kernel,
+// aligned16 (f1, f2, out and the distance between output images allow 16-byte accesses) and ws_bytes (of a 16-byte aligned workspace,
+// 0 = none) are what only the run knows; a size query plans an aligned call that brings all the workspace the plan wants.
+static CorrPlan corr_plan(const Settings &st, int N, int C, int H, int W, int md, int kernel, int s1, int s2, int pad, int is_multiply,
+                          bool aligned16 = true, size_t ws_bytes = (size_t)-1) {
+  CorrPlan pl;
+  memset(&pl, 0, sizeof(pl));
+  pl.family = CorrFamily::Generic;
+  pl.D = 2 * (md / s2) + 1;
+  const int D = pl.D;
+  if ((st.t.path_generic & 1) || kernel != 1 || s1 != 1 || s2 != 1 || pad != md || !is_multiply || (D != 9 && D != 5) || W % 4 != 0 ||
+      !aligned16)
+    return pl;
+  const size_t out_elems = (size_t)N * D * D * H * W;   // pad == md, stride 1: one output pixel per input pixel
+  const CorrForm *form = corr_form(st.t.corr_variant);   // nullptr: the library chooses
+  const bool chosen = form == nullptr;
+  const CorrForm *gramk = chosen ? corr_gramk_plan(N, C, H, W, st) : nullptr;
+  // the tiniest levels (level 6): direct kernel, L1/L2-resident operands, channel slices inside the block
+  if (corr_direct_shape_ok(W, D) && (st.t.corr_direct == 1 || (st.t.corr_direct == 0 && (long)H * W < 180 && chosen && !gramk))) {
+    pl.family = CorrFamily::Direct;
+    pl.store_policy = store_policy_for(st, out_elems * 4, 2, -1);
+    return pl;
+  }
+  if (chosen) form = gramk ? gramk : corr_tile_form(N, H, W, D);
+  if (chosen && !gramk && C == 32 && W % 8 == 0 && form == &kCorrForms[kCorrDma1]) {
+    // level 2 (32 channels, >= 400 tiles): the Gram band on the matrix cores.  Same box, same session (profiles/
+    // r04_corr_gram_experiments.md section 7): level 2 of 384x512 at batch 8 back to back 10.45 against 13.2 us, rocprofv3 average
+    // 12.65 against 15.6 us, inside the pass 12.3-12.5 us = 0.57-0.58 of 8 TB/s against 14.2 us = 0.50; 448x1024 at batch 4 13.7
+    // against 17.6 us; on buffers rotated through more than the Infinity Cache a tie (17.95 against 17.3-17.8 us).
+    // Under MFN_ARITH_FP32 the same band on the fp32 matrix instruction (form 46: raw operands, an fmaf chain over the channels
+    // in order, bitwise): 12.5 us against corr_dma_kernel's 14.0 back to back (corr.form = 16 keeps the latter)
+    const CorrForm *asked = corr_form(st.t.corr_form);
+    if (st.corr != 0) form = asked && asked->family == CorrFamily::Gram ? asked : &kCorrForms[kCorrGramBf16];
+    else if (asked != &kCorrForms[kCorrDma1]) form = &kCorrForms[kCorrGramF32];
+  }
+  // level 3 (64 channels, 128-399 tiles): the same band with a two-chunk K loop (form 48 only; corr.form = 20 keeps corr_dma_kernel's
+  // two channel groups: 9.95 -> 8.30 us back to back at 384x512 / batch 8, 10.04 -> 8.37 at 448x1024 / batch 4, profiles/r06_corr_l3.txt)
+  if (chosen && !gramk && C == 64 && W % 8 == 0 && form == &kCorrForms[kCorrDma2] && st.corr != 0 &&
+      corr_form(st.t.corr_form) != &kCorrForms[kCorrDma2])
+    form = &kCorrForms[kCorrGramBf16];
+  pl.form = form;
+  if (form->family == CorrFamily::Gram) {   // its own tiling, no channel slices; 64 channels: the bf16 form's two-chunk K loop only
+    pl.rows = corr_gram_rows(N, H, W, st.t.corr_rows, C);
+    if ((C == 32 || (C == 64 && form->terms == 5 && W % 8 == 0)) && corr_gram_range_ok(N, H, W, pl.rows)) {
+      pl.family = CorrFamily::Gram;
+      pl.store_policy = store_policy_for(st, out_elems * 4, 2, -1);
+      return pl;
+    }
+  }
+  if (form->family == CorrFamily::GramK && corr_gramk_shape_ok(C, W)) {   // coarse levels: channels over the waves of a block
+    pl.family = CorrFamily::GramK;
+    pl.store_policy = st.t.store_policy >= 0 ? st.t.store_policy : 0;
+    return pl;
+  }
+  if (form->family != CorrFamily::Tiled && form->family != CorrFamily::Dma)   // asked for, but not a level that kernel takes
+    form = corr_tile_form(N, H, W, D);
+  if (W < 32 && !(form->row_pairs && W >= 16)) form = &kCorrForms[kCorrTiled];   // the 32x4-tile kernels want full-width tiles
+  else if (form->family == CorrFamily::Tiled) form = &kCorrForms[kCorrDma1];      // corr_tiled_kernel only runs below 32 columns
+  pl.form = form;
+  pl.family = form->family;
+  pl.tile_w = form->family == CorrFamily::Dma ? 32 : (W >= 16 ? 16 : 8);
+  pl.tile_h = form->family == CorrFamily::Dma ? 4 : 256 / pl.tile_w;
+  const long tiles = (long)N * cdiv(W, pl.tile_w) * cdiv(H, pl.tile_h);
+  int slices = 1;  // few tiles, many channels: split channels until every CU has a block
+  if (tiles < 128 && form->groups == 1)  // the grouped tile kernels split the channels inside the block instead
+    while (tiles * slices < 256 && C / (slices * 2) >= 8 && slices < 32) slices *= 2;
+  if (slices > C / 4) slices = C / 4 > 0 ? C / 4 : 1;
+  if (slices > 1 && ws_bytes < (size_t)slices * out_elems * sizeof(float))
+    slices = 1;  // no (or too small a) workspace: single pass over all channels, still correct
+  pl.slices = slices;
+  pl.ws_bytes = slices > 1 ? (size_t)slices * out_elems * sizeof(float) : 0;
+  pl.store_policy = store_policy_for(st, out_elems * 4, 2, -1);
+  return pl;
+}
+
+size_t MFN_API(correlation_workspace_bytes)(int N, int C, int H, int W, int md, int kernel, int s1, int s2, int pad,
+                                            int is_multiply) {
+  if (N <= 0 || C <= 0 || corr_shape(H, W, md, kernel, s1, s2, pad, nullptr, nullptr, nullptr)) return 0;
+  return corr_plan(settings_now(), N, C, H, W, md, kernel, s1, s2, pad, is_multiply).ws_bytes;
+}
+
+static int corr_fwd_common(const Settings &st, const float *d1, const float *d2, float *out, int N, int C, int H, int W, int md, int kernel,
                            int s1, int s2, int pad, int is_multiply, int act, void *workspace, size_t ws_bytes,
                            void *stream, long long out_batch_stride = 0) {
   if (N != 0 && (!d1 || !d2 || !out)) return fail(MFN_E_NULL, "correlation_fwd: NULL tensor pointer");
@@ -214,71 +244,61 @@ static int corr_fwd_common(const float *d1, const float *d2, float *out, int N, 
     return fail(MFN_E_PARAM, "correlation_fwd: displaced window leaves the padded input (pad_size=%d < max_displacement=%d?)", pad, md);
   if (N == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
-  const int D = 2 * r + 1;
   // out may be a channel slice of a wider (N, Ctot, h, w) buffer: images then sit out_batch_stride elements apart
   const size_t img_elems = (size_t)tc * th * tw;
   if (out_batch_stride != 0 && (out_batch_stride < 0 || (size_t)out_batch_stride < img_elems))
     return fail(MFN_E_PARAM, "correlation_fwd: out_batch_stride=%lld is smaller than one image of the output (%zu)",
                 out_batch_stride, img_elems);
   const size_t onst = out_batch_stride ? (size_t)out_batch_stride : img_elems;
-  const bool out16 = aligned(out, 16) && onst % 4 == 0;  // 16-byte stores of the tiled kernels
-  // the tiniest levels (level 6): direct kernel, L1/L2-resident operands, channel slices inside the block
-  if ((g_tuning.path_generic & 1) == 0 && kernel == 1 && s1 == 1 && s2 == 1 && pad == md && is_multiply && (D == 9 || D == 5) &&
-      W % 4 == 0 && aligned(d1, 16) && aligned(d2, 16) && out16 &&
-      (g_tuning.corr_direct == 1 || (g_tuning.corr_direct == 0 && (long)H * W < 180 && g_tuning.corr_variant < 0 &&
-                                     !corr_gramk_plan(N, C, H, W, D)))) {
-    CorrDirectParams dp;
-    memset(&dp, 0, sizeof(dp));
-    dp.f1 = d1; dp.f2 = d2; dp.out = out; dp.out_nstride = onst; dp.st_policy = store_policy_for((size_t)N * img_elems * 4, 2, -1);
-    dp.N = N; dp.C = C; dp.H = H; dp.W = W;
-    dp.sumelems = (float)C;
-    dp.inv_sumelems = 1.0f / (float)C;
-    dp.exact_div = (C & (C - 1)) != 0;
-    dp.leaky = act;
-    dp.max_slices = 32;  // measured: 7.9 us at level 6 (8x196x6x8) against 9.2 us with 49 four-channel slices
-    rc = D == 9 ? corr_direct_launch<9>(dp, s) : corr_direct_launch<5>(dp, s);
-    if (rc >= 0) return hipfail(rc, "correlation_fwd(direct)");
+  const CorrPlan pl = corr_plan(st, N, C, H, W, md, kernel, s1, s2, pad, is_multiply,
+                                aligned(d1, 16) && aligned(d2, 16) && aligned(out, 16) && onst % 4 == 0,
+                                workspace && aligned(workspace, 16) ? ws_bytes : 0);
+  const bool d9 = pl.D == 9;
+  switch (pl.family) {
+    case CorrFamily::Generic: {
+      CorrGenericParams g{d1, d2, out, N, C, H, W, md, kernel, s1, s2, pad, is_multiply ? 1 : 0, tc, th, tw, r, pl.D, act, onst};
+      return hipfail(corr_generic_launch(g, s), "correlation_fwd(generic)");
+    }
+    case CorrFamily::Direct: {
+      CorrDirectParams dp;
+      memset(&dp, 0, sizeof(dp));
+      dp.f1 = d1; dp.f2 = d2; dp.out = out; dp.out_nstride = onst; dp.st_policy = pl.store_policy;
+      dp.N = N; dp.C = C; dp.H = H; dp.W = W;
+      dp.sumelems = (float)C;
+      dp.inv_sumelems = 1.0f / (float)C;
+      dp.exact_div = (C & (C - 1)) != 0;
+      dp.leaky = act;
+      dp.max_slices = 32;  // measured: 7.9 us at level 6 (8x196x6x8) against 9.2 us with 49 four-channel slices
+      return hipfail(d9 ? corr_direct_launch<9>(dp, s) : corr_direct_launch<5>(dp, s), "correlation_fwd(direct)");
+    }
+    case CorrFamily::Gram: {
+      CorrGramParams gp;
+      memset(&gp, 0, sizeof(gp));
+      gp.f1 = d1; gp.f2 = d2; gp.out = out; gp.out_nstride = onst;
+      gp.N = N; gp.H = H; gp.W = W; gp.C = C;
+      gp.rows = pl.rows;
+      gp.store_policy = pl.store_policy;   // full lines, written through like every other cost volume >= 4 MB
+      gp.leaky = act;
+      gp.xcd_swizzle = 1;
+      gp.inv_c = 1.0f / (float)C;
+      gp.timeline = (unsigned long long *)g_timeline;
+      return hipfail(d9 ? corr_gram_form<9>(gp, *pl.form, s) : corr_gram_form<5>(gp, *pl.form, s), "correlation_fwd(gram)");
+    }
+    case CorrFamily::GramK: {
+      CorrGramKParams kp;
+      memset(&kp, 0, sizeof(kp));
+      kp.f1 = d1; kp.f2 = d2; kp.out = out; kp.out_nstride = onst;
+      kp.N = N; kp.C = C; kp.H = H; kp.W = W;
+      kp.store_policy = pl.store_policy;
+      kp.leaky = act;
+      kp.xcd_swizzle = 1;
+      kp.sumelems = (float)C;
+      kp.inv_sumelems = 1.0f / (float)C;
+      kp.exact_div = (C & (C - 1)) != 0;
+      return hipfail(d9 ? corr_gramk_form<9>(kp, *pl.form, s) : corr_gramk_form<5>(kp, *pl.form, s), "correlation_fwd(gramk)");
+    }
+    default: break;   // Tiled / Dma
   }
-  int twc = 0, variant = 0;
-  int slices = corr_plan(N, C, H, W, md, kernel, s1, s2, pad, is_multiply, &twc, &variant);
-  if (slices > 0 && !(aligned(d1, 16) && aligned(d2, 16) && out16)) slices = 0;
-  if (slices == 0) {
-    CorrGenericParams g{d1, d2, out, N, C, H, W, md, kernel, s1, s2, pad, is_multiply ? 1 : 0, tc, th, tw, r, D, act, onst};
-    return hipfail(corr_generic_launch(g, s), "correlation_fwd(generic)");
-  }
-  if (corr_variant_gram(variant)) {
-    CorrGramParams gp;
-    memset(&gp, 0, sizeof(gp));
-    gp.f1 = d1; gp.f2 = d2; gp.out = out; gp.out_nstride = onst;
-    gp.N = N; gp.H = H; gp.W = W; gp.C = C;
-    gp.rows = corr_gram_rows(N, H, W, g_tuning.corr_rows, C);
-    // cooperative form (variant 40): full lines, written through like every other cost volume >= 4 MB; the others store plain
-    gp.store_policy = g_tuning.store_policy >= 0 ? g_tuning.store_policy
-                                                 : (corr_variant_gram(variant) ? store_policy_for((size_t)N * img_elems * 4, 2, -1) : 0);
-    gp.leaky = act;
-    gp.xcd_swizzle = 1;
-    gp.inv_c = 1.0f / (float)C;
-    gp.timeline = (unsigned long long *)g_timeline;
-    rc = (D == 9) ? corr_gram_variant<9>(gp, variant, s) : corr_gram_variant<5>(gp, variant, s);
-    return hipfail(rc, "correlation_fwd(gram)");
-  }
-  if (corr_variant_gramk(variant)) {
-    CorrGramKParams kp;
-    memset(&kp, 0, sizeof(kp));
-    kp.f1 = d1; kp.f2 = d2; kp.out = out; kp.out_nstride = onst;
-    kp.N = N; kp.C = C; kp.H = H; kp.W = W;
-    kp.store_policy = g_tuning.store_policy >= 0 ? g_tuning.store_policy : 0;
-    kp.leaky = act;
-    kp.xcd_swizzle = 1;
-    kp.sumelems = (float)C;
-    kp.inv_sumelems = 1.0f / (float)C;
-    kp.exact_div = (C & (C - 1)) != 0;
-    rc = (D == 9) ? corr_gramk_variant<9>(kp, variant, s) : corr_gramk_variant<5>(kp, variant, s);
-    return hipfail(rc, "correlation_fwd(gramk)");
-  }
-  const size_t out_elems = (size_t)N * tc * th * tw;
-  if (slices > 1 && (!workspace || ws_bytes < (size_t)slices * out_elems * sizeof(float) || !aligned(workspace, 16)))
-    slices = 1;  // no (or too small a) workspace: single pass over all channels, still correct
   CorrParams p;
   p.f1 = d1; p.f2 = d2; p.out = out; p.out_nstride = onst;
   p.N = N; p.C = C; p.H = H; p.W = W;
@@ -287,16 +307,16 @@ static int corr_fwd_common(const float *d1, const float *d2, float *out, int N, 
   p.inv_sumelems = 1.0f / (float)C;
   p.exact_div = (C & (C - 1)) != 0;  // 1/C is exact only for powers of two
   p.xcd_swizzle = 1;
-  p.nt_store = store_policy_for((size_t)N * img_elems * 4, 2, -1);
+  p.nt_store = pl.store_policy;
   p.leaky = act;
   p.timeline = (unsigned long long *)g_timeline;
-  p.nslices = slices;
-  p.slice_channels = slices > 1 ? ((cdiv(C, slices) + 3) / 4) * 4 : C;
+  p.nslices = pl.slices;
+  p.slice_channels = pl.slices > 1 ? ((cdiv(C, pl.slices) + 3) / 4) * 4 : C;
   p.partial = (float *)workspace;
-  rc = (D == 9) ? corr_dispatch_tw<9>(p, twc, variant, s) : corr_dispatch_tw<5>(p, twc, variant, s);
+  rc = d9 ? corr_tile_launch<9>(p, pl, s) : corr_tile_launch<5>(p, pl, s);
   if (rc) return hipfail(rc, "correlation_fwd");
-  if (slices > 1) {
-    CorrReduceParams rp{(const float *)workspace, out, out_elems / 4, slices, p.inv_sumelems, p.sumelems, p.exact_div, act,
+  if (pl.slices > 1) {
+    CorrReduceParams rp{(const float *)workspace, out, (size_t)N * img_elems / 4, pl.slices, p.inv_sumelems, p.sumelems, p.exact_div, act,
                         img_elems / 4, onst / 4};
     rc = corr_reduce_launch(rp, s);
   }
@@ -306,26 +326,26 @@ static int corr_fwd_common(const float *d1, const float *d2, float *out, int N, 
 int MFN_API(correlation_fwd_ws)(const float *d1, const float *d2, float *out, int N, int C, int H, int W, int md,
                                 int kernel, int s1, int s2, int pad, int is_multiply, void *workspace,
                                 size_t ws_bytes, void *stream) {
-  return corr_fwd_common(d1, d2, out, N, C, H, W, md, kernel, s1, s2, pad, is_multiply, 0, workspace, ws_bytes, stream);
+  return corr_fwd_common(settings_now(), d1, d2, out, N, C, H, W, md, kernel, s1, s2, pad, is_multiply, 0, workspace, ws_bytes, stream);
 }
 
 int MFN_API(correlation_fwd_act)(const float *d1, const float *d2, float *out, int N, int C, int H, int W, int md,
                                  int kernel, int s1, int s2, int pad, int is_multiply, int activation, void *workspace,
                                  size_t ws_bytes, void *stream) {
-  return corr_fwd_common(d1, d2, out, N, C, H, W, md, kernel, s1, s2, pad, is_multiply, activation, workspace, ws_bytes,
+  return corr_fwd_common(settings_now(), d1, d2, out, N, C, H, W, md, kernel, s1, s2, pad, is_multiply, activation, workspace, ws_bytes,
                          stream);
 }
 
 int MFN_API(correlation_fwd_into)(const float *d1, const float *d2, float *out, long long out_batch_stride, int N, int C,
                                   int H, int W, int md, int kernel, int s1, int s2, int pad, int is_multiply,
                                   int activation, void *workspace, size_t ws_bytes, void *stream) {
-  return corr_fwd_common(d1, d2, out, N, C, H, W, md, kernel, s1, s2, pad, is_multiply, activation, workspace, ws_bytes,
+  return corr_fwd_common(settings_now(), d1, d2, out, N, C, H, W, md, kernel, s1, s2, pad, is_multiply, activation, workspace, ws_bytes,
                          stream, out_batch_stride);
 }
 
 int MFN_API(correlation_fwd)(const float *d1, const float *d2, float *out, int N, int C, int H, int W, int md,
                              int kernel, int s1, int s2, int pad, int is_multiply, void *stream) {
-  return corr_fwd_common(d1, d2, out, N, C, H, W, md, kernel, s1, s2, pad, is_multiply, 0, nullptr, 0, stream);
+  return corr_fwd_common(settings_now(), d1, d2, out, N, C, H, W, md, kernel, s1, s2, pad, is_multiply, 0, nullptr, 0, stream);
 }
 
 // ---- warp -------------------------------------------------------------------------------------------
@@ -335,7 +355,7 @@ int MFN_API(warp_fwd)(const float *x, const float *flow, float *out, int N, int 
   if (N < 0 || C <= 0 || H <= 0 || W <= 0) return fail(MFN_E_SHAPE, "warp_fwd: N=%d C=%d H=%d W=%d", N, C, H, W);
   if (!aligned(x, 4) || !aligned(flow, 4) || !aligned(out, 4)) return fail(MFN_E_ALIGN, "warp_fwd: unaligned pointer");
   if (N == 0) return 0;
-  WarpParams p{x, flow, out, N, C, H, W, clip ? 1 : 0, store_policy_for((size_t)N * C * H * W * 4, 1, -1)};
+  WarpParams p{x, flow, out, N, C, H, W, clip ? 1 : 0, store_policy_for(settings_now(), (size_t)N * C * H * W * 4, 1, -1)};
   return hipfail(warp_fwd_launch(p, (hipStream_t)stream), "warp_fwd");
 }
 
@@ -377,8 +397,8 @@ int MFN_API(deform_conv_out_shape)(int H, int W, int kh, int kw, int sh, int sw,
   return 0;
 }
 
-static bool dc_mfma_ok(int kh, int kw, int groups, int dg) {
-  return (g_tuning.path_generic & 2) == 0 && kh == 3 && kw == 3 && groups == 1 && dg == 1;
+static bool dc_mfma_ok(const Settings &st, int kh, int kw, int groups, int dg) {
+  return (st.t.path_generic & 2) == 0 && kh == 3 && kw == 3 && groups == 1 && dg == 1;
 }
 
 // ---- launch plan of the MFMA path: tiling, K split and workspace layout -----------------------------------
@@ -400,7 +420,7 @@ static bool dcm_config_ok(int mt, int pt, int kw) {
   return false;
 }
 // mma_shape: the call has the operator shape dc_mma_kernel takes (dcm_shape_ok)
-static DcPlan dc_plan(int Cin, int Cout, int N, int Ho, int Wo, bool mma_shape) {
+static DcPlan dc_plan(const Settings &st, int Cin, int Cout, int N, int Ho, int Wo, bool mma_shape) {
   DcPlan pl;
   memset(&pl, 0, sizeof(pl));
   const long P = (long)N * Ho * Wo;
@@ -418,7 +438,7 @@ static DcPlan dc_plan(int Cin, int Cout, int N, int Ho, int Wo, bool mma_shape) 
     pl.ntiles = (int)((P + 31) / 32);
   }
   const long tiles = pl.ntiles;
-  if (mma_shape && t_arith.deform != 0) {
+  if (mma_shape && st.deform != 0) {
     // ---- dc_mma_kernel: B operands shared by the MT filter tiles of a wave; K slices in whole 16-channel groups ----
     pl.mma = 2;
     pl.groups = Cin / 16;
@@ -438,8 +458,8 @@ static DcPlan dc_plan(int Cin, int Cout, int N, int Ho, int Wo, bool mma_shape) 
     }
     else if (mtiles == 3 && pl.groups % 6 == 0) { cmt = 3; ckw = 6; }
     else if (tiles >= 1024) { cpt = 4; ckw = 1; }
-    if (g_tuning.dc_mt > 0 && g_tuning.dc_pt > 0 && g_tuning.dc_nw > 0) {     // measurement: an explicit (mt, pt, waves per block)
-      cmt = g_tuning.dc_mt; cpt = g_tuning.dc_pt; ckw = g_tuning.dc_nw / (cpt > 0 ? cpt : 1);
+    if (st.t.dc_mt > 0 && st.t.dc_pt > 0 && st.t.dc_nw > 0) {     // measurement: an explicit (mt, pt, waves per block)
+      cmt = st.t.dc_mt; cpt = st.t.dc_pt; ckw = st.t.dc_nw / (cpt > 0 ? cpt : 1);
     }
     if (!dcm_config_ok(cmt, cpt, ckw) || pl.groups % ckw != 0 || cmt > mtiles) { cmt = 1; cpt = 1; ckw = 1; }
     pl.mt = cmt; pl.pt = cpt; pl.kw = ckw; pl.nw = cpt * ckw; pl.ksb = 1;
@@ -457,7 +477,7 @@ static DcPlan dc_plan(int Cin, int Cout, int N, int Ho, int Wo, bool mma_shape) 
   pl.mma = 0;
   pl.mgroups = (mtiles + mt - 1) / mt;
   const int ncp = (Cin + 1) / 2;
-  int pt = g_tuning.dc_pt;
+  int pt = st.t.dc_pt;
   if (!(pt == 1 || pt == 2 || pt == 4)) {
     // cycles of the slowest SIMD: residency rounds (3 blocks of 4 waves per CU) x [channel pairs per wave x (576 MFMA +
     // ~170 VALU) + setup + epilogue] -- the measured per-block phases (profiles/r01b_deform_pmc_and_timelines.md);
@@ -475,12 +495,12 @@ static DcPlan dc_plan(int Cin, int Cout, int N, int Ho, int Wo, bool mma_shape) 
   pl.pt = pt;
   // 8-wave blocks (twice the in-block K slices) where the whole launch is at most one block per CU and every wave still
   // gets a few channel pairs: the coarsest level (192 blocks, 64 pairs) is a latency chain per wave, not a throughput job
-  int nw = g_tuning.dc_nw;
+  int nw = st.t.dc_nw;
   if (nw != 4 && nw != 8) nw = (mt == 1 && pt == 1 && ((tiles + pt - 1) / pt) * pl.mgroups <= 256 && ncp >= 32) ? 8 : 4;
   if (nw == 8 && !(mt == 1 && pt == 1)) nw = 4;  // the only 8-wave instantiation
   pl.nw = nw;
   const int kw = nw / pt, kc = dc_kc(mt, kw);
-  int ksb = g_tuning.dc_ksb;
+  int ksb = st.t.dc_ksb;
   if (ksb <= 0) {  // few pixel tiles (coarse levels): split K across workgroups until the chip is covered
     ksb = 1;
     const long blocks0 = ((tiles + pt - 1) / pt) * pl.mgroups;
@@ -523,18 +543,19 @@ static int dc_pack(const DcPlan &pl, const float *w, float *packed, int Cin, int
 
 size_t MFN_API(deform_conv_workspace_bytes)(int N, int Cin, int H, int W, int Cout, int kh, int kw, int sh, int sw,
                                             int ph, int pw, int dh, int dw, int groups, int deform_groups) {
+  const Settings st = settings_now();
   (void)groups; (void)deform_groups;
   int Ho, Wo;
   if (N <= 0 || Cin <= 0 || Cout <= 0 || MFN_API(deform_conv_out_shape)(H, W, kh, kw, sh, sw, ph, pw, dh, dw, &Ho, &Wo))
     return 0;
-  if (!dc_mfma_ok(kh, kw, groups, deform_groups)) return 0;  // generic kernel needs no workspace
+  if (!dc_mfma_ok(st, kh, kw, groups, deform_groups)) return 0;  // generic kernel needs no workspace
   // the larger of the two plans: a call whose x / out are not 16-byte aligned (a view at an odd offset) cannot take the matrix-core
   // kernel and runs the fp32 kernel's plan instead (dc_run), with the same workspace
   const bool mma = dc_mma_shape(N, Cin, H, W, kh, kw, sh, sw, ph, pw, dh, dw, groups, deform_groups);
-  const DcPlan pl = dc_plan(Cin, Cout, N, Ho, Wo, mma);
+  const DcPlan pl = dc_plan(st, Cin, Cout, N, Ho, Wo, mma);
   size_t need = pl.wt_bytes + pl.partial_bytes;
   if (mma) {
-    const DcPlan alt = dc_plan(Cin, Cout, N, Ho, Wo, false);
+    const DcPlan alt = dc_plan(st, Cin, Cout, N, Ho, Wo, false);
     if (alt.wt_bytes + alt.partial_bytes > need) need = alt.wt_bytes + alt.partial_bytes;
   }
   return need;
@@ -542,31 +563,33 @@ size_t MFN_API(deform_conv_workspace_bytes)(int N, int Cin, int H, int W, int Co
 
 size_t MFN_API(deform_conv_packed_weight_bytes)(int N, int Cin, int H, int W, int Cout, int kh, int kw, int sh, int sw,
                                                 int ph, int pw, int dh, int dw, int groups, int deform_groups) {
+  const Settings st = settings_now();
   int Ho, Wo;
   if (N <= 0 || Cin <= 0 || Cout <= 0 || groups < 1 || Cin % groups ||
       MFN_API(deform_conv_out_shape)(H, W, kh, kw, sh, sw, ph, pw, dh, dw, &Ho, &Wo))
     return 0;
-  if (!dc_mfma_ok(kh, kw, groups, deform_groups)) return (size_t)Cout * (Cin / groups) * kh * kw * sizeof(float);
-  return dc_plan(Cin, Cout, N, Ho, Wo, dc_mma_shape(N, Cin, H, W, kh, kw, sh, sw, ph, pw, dh, dw, groups, deform_groups)).wt_bytes;
+  if (!dc_mfma_ok(st, kh, kw, groups, deform_groups)) return (size_t)Cout * (Cin / groups) * kh * kw * sizeof(float);
+  return dc_plan(st, Cin, Cout, N, Ho, Wo, dc_mma_shape(N, Cin, H, W, kh, kw, sh, sw, ph, pw, dh, dw, groups, deform_groups)).wt_bytes;
 }
 
 int MFN_API(deform_conv_pack_weights)(const float *w, int N, int Cin, int H, int W, int Cout, int kh, int kw, int sh,
                                       int sw, int ph, int pw, int dh, int dw, int groups, int deform_groups,
                                       void *packed, size_t packed_bytes, unsigned long long *layout_tag,
                                       void *stream) {
+  const Settings st = settings_now();
   if (!w || !packed || !layout_tag) return fail(MFN_E_NULL, "deform_conv_pack_weights: NULL pointer");
   const size_t need = MFN_API(deform_conv_packed_weight_bytes)(N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, deform_groups);
   if (!need) return fail(MFN_E_SHAPE, "deform_conv_pack_weights: bad shape");
   if (packed_bytes < need) return fail(MFN_E_WORKSPACE, "deform_conv_pack_weights: %zu bytes required (got %zu)", need, packed_bytes);
   if (!aligned(packed, 16)) return fail(MFN_E_ALIGN, "deform_conv_pack_weights: packed buffer must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
-  if (!dc_mfma_ok(kh, kw, groups, deform_groups)) {
+  if (!dc_mfma_ok(st, kh, kw, groups, deform_groups)) {
     *layout_tag = kDcPlainTag;
     return hipfail(dc_copy_launch(w, (float *)packed, need / sizeof(float), s), "deform_conv_pack_weights");
   }
   int Ho, Wo;
   MFN_API(deform_conv_out_shape)(H, W, kh, kw, sh, sw, ph, pw, dh, dw, &Ho, &Wo);
-  const DcPlan pl = dc_plan(Cin, Cout, N, Ho, Wo, dc_mma_shape(N, Cin, H, W, kh, kw, sh, sw, ph, pw, dh, dw, groups, deform_groups));
+  const DcPlan pl = dc_plan(st, Cin, Cout, N, Ho, Wo, dc_mma_shape(N, Cin, H, W, kh, kw, sh, sw, ph, pw, dh, dw, groups, deform_groups));
   *layout_tag = dc_layout_tag(pl);
   return hipfail(dc_pack(pl, w, (float *)packed, Cin, Cout, s), "deform_conv_pack_weights");
 }
@@ -574,9 +597,9 @@ int MFN_API(deform_conv_pack_weights)(const float *w, int N, int Cin, int H, int
 // packed == nullptr: stateless operator call, the filter bank is re-packed into the head of the workspace
 // (MXNet hands the operator its weights on every call).  packed != nullptr: the caller packed it once with
 // mfn_deform_conv_pack_weights (inference: weights are constants) and the workspace only holds partial sums.
-static int dc_run(DeformParams &p, const void *packed, size_t packed_bytes, unsigned long long tag, void *workspace,
+static int dc_run(const Settings &st, DeformParams &p, const void *packed, size_t packed_bytes, unsigned long long tag, void *workspace,
                   size_t ws_bytes, hipStream_t s, const char *what) {
-  if (!dc_mfma_ok(p.kh, p.kw, p.groups, p.dg)) {
+  if (!dc_mfma_ok(st, p.kh, p.kw, p.groups, p.dg)) {
     if (packed) {  // plain copy of w for shapes the MFMA path does not take
       if (tag != kDcPlainTag)
         return fail(MFN_E_WORKSPACE, "%s: packed weights were laid out under another tuning (re-run mfn_deform_conv_pack_weights)", what);
@@ -589,7 +612,7 @@ static int dc_run(DeformParams &p, const void *packed, size_t packed_bytes, unsi
   // weights packed for the matrix-core layout cannot follow and are refused below (MFN_E_ALIGN).
   bool mma_shape = dcm_shape_ok(p.N, p.Cin, p.H, p.W, p.Ho, p.Wo, p.kh, p.kw, p.sh, p.sw, p.ph, p.pw, p.dh, p.dw, p.groups, p.dg);
   if (mma_shape && !packed && (!aligned(p.x, 16) || !aligned(p.out, 16))) mma_shape = false;
-  const DcPlan pl = dc_plan(p.Cin, p.Cout, p.N, p.Ho, p.Wo, mma_shape);
+  const DcPlan pl = dc_plan(st, p.Cin, p.Cout, p.N, p.Ho, p.Wo, mma_shape);
   const size_t need = (packed ? 0 : pl.wt_bytes) + pl.partial_bytes;
   if (need && (!workspace || ws_bytes < need))
     return fail(MFN_E_WORKSPACE, "%s: workspace of %zu bytes required (got %zu)", what, need, workspace ? ws_bytes : (size_t)0);
@@ -608,9 +631,9 @@ static int dc_run(DeformParams &p, const void *packed, size_t packed_bytes, unsi
     p.wt = (const float *)workspace;
     partial_base += pl.wt_bytes;
   }
-  p.allow_fast = (g_tuning.dc_off & 2) ? 0 : 1;
+  p.allow_fast = (st.t.dc_off & 2) ? 0 : 1;
   p.timeline = (unsigned long long *)g_timeline;
-  p.stage_window = (g_tuning.dc_off & 1) ? 0 : 1;
+  p.stage_window = (st.t.dc_off & 1) ? 0 : 1;
   {
     // blockIdx.x -> tile range per XCD: the dispatch order is x fastest, so with several filter groups (grid z) block
     // (x, z) still runs on XCD x % 8 as long as gridDim.x is a multiple of 8
@@ -620,7 +643,7 @@ static int dc_run(DeformParams &p, const void *packed, size_t packed_bytes, unsi
   }
   // plain: the warped features are read next by the correlation of the same level, whose block order puts image k on the
   // same XCD as this kernel's -- written through (nt) they would leave that L2 (level-2 correlation +1 us inside the pass)
-  p.st_policy = store_policy_for((size_t)p.N * p.Cout * p.Ho * p.Wo * 4, 0, -1);
+  p.st_policy = store_policy_for(st, (size_t)p.N * p.Cout * p.Ho * p.Wo * 4, 0, -1);
   p.vec_store = (p.Wo % 4 == 0) && aligned(p.out, 16) && aligned(workspace, 16) && pl.wt_bytes % 16 == 0;
   p.ncp_pad = pl.ncp_pad;
   p.cps_per_slice = pl.cps_per_slice;
@@ -677,7 +700,7 @@ static int dc_check(const char *what, const void *x, const void *w, const void *
   return 0;
 }
 
-static int dc_fwd_common(const char *what, const float *x, const float *offset, const float *w, const void *packed,
+static int dc_fwd_common(const Settings &st, const char *what, const float *x, const float *offset, const float *w, const void *packed,
                          size_t packed_bytes, unsigned long long tag, const float *bias, float *out, int N, int Cin, int H, int W, int Cout,
                          int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int groups, int dg,
                          void *workspace, size_t ws_bytes, void *stream) {
@@ -693,10 +716,10 @@ static int dc_fwd_common(const char *what, const float *x, const float *offset, 
   p.N = N; p.Cin = Cin; p.H = H; p.W = W; p.Cout = Cout; p.CoutP = Cout; p.Ho = Ho; p.Wo = Wo;
   p.kh = kh; p.kw = kw; p.sh = sh; p.sw = sw; p.ph = ph; p.pw = pw; p.dh = dh; p.dw = dw;
   p.groups = groups; p.dg = dg; p.P = N * Ho * Wo; p.allow_fast = 1;
-  return dc_run(p, packed, packed_bytes, tag, workspace, ws_bytes, (hipStream_t)stream, what);
+  return dc_run(st, p, packed, packed_bytes, tag, workspace, ws_bytes, (hipStream_t)stream, what);
 }
 
-static int dc_shared_common(const char *what, const float *x, const float *flow, float flow_scale, float flow_stride,
+static int dc_shared_common(const Settings &st, const char *what, const float *x, const float *flow, float flow_scale, float flow_stride,
                             const float *w, const void *packed, size_t packed_bytes, unsigned long long tag,
                             const float *bias, const float *ep_mask, const float *ep_add, int ep_act, float *out, int N, int Cin, int H, int W, int Cout, int kh, int kw, int ph, int pw, int dh, int dw,
                             int groups, void *workspace, size_t ws_bytes, void *stream) {
@@ -716,13 +739,13 @@ static int dc_shared_common(const char *what, const float *x, const float *flow,
   p.kh = kh; p.kw = kw; p.sh = 1; p.sw = 1; p.ph = ph; p.pw = pw; p.dh = dh; p.dw = dw;
   p.groups = groups; p.dg = 1; p.P = N * Ho * Wo; p.allow_fast = 1;
   p.ep_mask = ep_mask; p.ep_add = ep_add; p.ep_leaky = ep_act;
-  return dc_run(p, packed, packed_bytes, tag, workspace, ws_bytes, (hipStream_t)stream, what);
+  return dc_run(st, p, packed, packed_bytes, tag, workspace, ws_bytes, (hipStream_t)stream, what);
 }
 
 int MFN_API(deform_conv_fwd)(const float *x, const float *offset, const float *w, const float *bias, float *out,
                              int N, int Cin, int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph, int pw,
                              int dh, int dw, int groups, int dg, void *workspace, size_t ws_bytes, void *stream) {
-  return dc_fwd_common("deform_conv_fwd", x, offset, w, nullptr, 0, 0, bias, out, N, Cin, H, W, Cout, kh, kw, sh, sw, ph,
+  return dc_fwd_common(settings_now(), "deform_conv_fwd", x, offset, w, nullptr, 0, 0, bias, out, N, Cin, H, W, Cout, kh, kw, sh, sw, ph,
                        pw, dh, dw, groups, dg, workspace, ws_bytes, stream);
 }
 
@@ -731,7 +754,7 @@ int MFN_API(deform_conv_fwd_packed)(const float *x, const float *offset, const v
                                     int kw, int sh, int sw, int ph, int pw, int dh, int dw, int groups, int dg,
                                     void *workspace, size_t ws_bytes, void *stream) {
   if (!packed) return fail(MFN_E_NULL, "deform_conv_fwd_packed: NULL packed weights");
-  return dc_fwd_common("deform_conv_fwd_packed", x, offset, nullptr, packed, packed_bytes, layout_tag, bias, out, N, Cin, H, W,
+  return dc_fwd_common(settings_now(), "deform_conv_fwd_packed", x, offset, nullptr, packed, packed_bytes, layout_tag, bias, out, N, Cin, H, W,
                        Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, dg, workspace, ws_bytes, stream);
 }
 
@@ -739,7 +762,7 @@ int MFN_API(deform_conv_shared_fwd)(const float *x, const float *flow, float flo
                                     const float *w, const float *bias, float *out, int N, int Cin, int H, int W,
                                     int Cout, int kh, int kw, int ph, int pw, int dh, int dw, int groups,
                                     void *workspace, size_t ws_bytes, void *stream) {
-  return dc_shared_common("deform_conv_shared_fwd", x, flow, flow_scale, flow_stride, w, nullptr, 0, 0, bias, nullptr, nullptr, 0, out, N, Cin,
+  return dc_shared_common(settings_now(), "deform_conv_shared_fwd", x, flow, flow_scale, flow_stride, w, nullptr, 0, 0, bias, nullptr, nullptr, 0, out, N, Cin,
                           H, W, Cout, kh, kw, ph, pw, dh, dw, groups, workspace, ws_bytes, stream);
 }
 
@@ -748,7 +771,7 @@ int MFN_API(deform_conv_shared_fwd_packed)(const float *x, const float *flow, fl
                                            const float *bias, float *out, int N, int Cin, int H, int W, int Cout, int kh, int kw, int ph, int pw,
                                            int dh, int dw, int groups, void *workspace, size_t ws_bytes, void *stream) {
   if (!packed) return fail(MFN_E_NULL, "deform_conv_shared_fwd_packed: NULL packed weights");
-  return dc_shared_common("deform_conv_shared_fwd_packed", x, flow, flow_scale, flow_stride, nullptr, packed,
+  return dc_shared_common(settings_now(), "deform_conv_shared_fwd_packed", x, flow, flow_scale, flow_stride, nullptr, packed,
                           packed_bytes, layout_tag, bias, nullptr, nullptr, 0, out, N, Cin, H, W, Cout, kh, kw, ph, pw, dh, dw,
                           groups, workspace, ws_bytes, stream);
 }
@@ -762,7 +785,7 @@ int MFN_API(deform_conv_matching_fwd)(const float *x, const float *flow, float f
   if (!w && !packed) return fail(MFN_E_NULL, "deform_conv_matching_fwd: neither weights nor packed weights");
   if (activation != 0 && activation != 1)
     return fail(MFN_E_PARAM, "deform_conv_matching_fwd: activation must be MFN_ACT_NONE or MFN_ACT_LEAKY_0_1");
-  return dc_shared_common("deform_conv_matching_fwd", x, flow, flow_scale, flow_stride, packed ? nullptr : w, packed,
+  return dc_shared_common(settings_now(), "deform_conv_matching_fwd", x, flow, flow_scale, flow_stride, packed ? nullptr : w, packed,
                           packed ? packed_bytes : 0, layout_tag, bias, mask, tradeoff, activation, out, N, Cin, H, W, Cout, kh,
                           kw, ph, pw, dh, dw, groups, workspace, ws_bytes, stream);
 }
@@ -772,7 +795,7 @@ int MFN_API(offsets_from_flow)(const float *flow, float *offset, int N, int H, i
   if (N != 0 && (!flow || !offset)) return fail(MFN_E_NULL, "offsets_from_flow: NULL tensor pointer");
   if (N < 0 || H <= 0 || W <= 0 || taps < 1) return fail(MFN_E_SHAPE, "offsets_from_flow: bad shape");
   if (stride == 0.f) return fail(MFN_E_PARAM, "offsets_from_flow: stride must be non-zero");
-  OffsetsParams p{flow, offset, N, H, W, taps, scale, stride, store_policy_for((size_t)N * 2 * taps * H * W * 4, 2, -1)};
+  OffsetsParams p{flow, offset, N, H, W, taps, scale, stride, store_policy_for(settings_now(), (size_t)N * 2 * taps * H * W * 4, 2, -1)};
   return hipfail(offsets_from_flow_launch(p, (hipStream_t)stream), "offsets_from_flow");
 }
 
@@ -783,7 +806,7 @@ int MFN_API(upsample_fwd)(const float *x, float *out, int N, int C, int H, int W
   if ((size_t)H * factor >= ((size_t)1 << 30) || (size_t)W * factor >= ((size_t)1 << 30))
     return fail(MFN_E_UNSUPPORTED, "upsample_fwd: output plane too large");
   if (N == 0) return 0;
-  UpsampleParams p{x, out, N, C, H, W, factor, store_policy_for((size_t)N * C * H * W * factor * factor * 4, 2, -1)};
+  UpsampleParams p{x, out, N, C, H, W, factor, store_policy_for(settings_now(), (size_t)N * C * H * W * factor * factor * 4, 2, -1)};
   return hipfail(upsample_launch(p, (hipStream_t)stream), "upsample_fwd");
 }
 
@@ -793,6 +816,7 @@ static bool req_ok(int r) { return r == MFN_REQ_NULL || r == MFN_REQ_WRITE || r 
 int MFN_API(correlation_bwd)(const float *gout, const float *d1, const float *d2, float *g1, float *g2, int N, int C,
                              int H, int W, int md, int kernel, int s1, int s2, int pad, int is_multiply, int req1,
                              int req2, void *stream) {
+  const Settings st = settings_now();
   if (N != 0 && (!gout || !d1 || !d2)) return fail(MFN_E_NULL, "correlation_bwd: NULL tensor pointer");
   if (N != 0 && ((req1 && !g1) || (req2 && !g2))) return fail(MFN_E_NULL, "correlation_bwd: NULL gradient output");
   if (!req_ok(req1) || !req_ok(req2)) return fail(MFN_E_PARAM, "correlation_bwd: req must be 0 (null), 1 (write) or 3 (add)");
@@ -805,13 +829,13 @@ int MFN_API(correlation_bwd)(const float *gout, const float *d1, const float *d2
   const int r = md / s2, D = 2 * r + 1;
   const size_t in_elems = (size_t)N * C * H * W;
   if (kernel == 1 && s1 == 1 && s2 == 1 && pad == md && is_multiply) {
-    CorrBwdParams p{gout, d1, d2, g1, g2, N, C, H, W, md, D, req1, req2, store_policy_for((size_t)N * C * H * W * 4, 2, -1)};
+    CorrBwdParams p{gout, d1, d2, g1, g2, N, C, H, W, md, D, req1, req2, store_policy_for(st, (size_t)N * C * H * W * 4, 2, -1)};
     const bool al16 = aligned(gout, 16) && aligned(d1, 16) && aligned(d2, 16) && (!g1 || aligned(g1, 16)) && (!g2 || aligned(g2, 16));
     if (W % 4 == 0 && (D == 9 || D == 5) && al16) {
       const size_t threads = (size_t)N * ((C + 3) / 4) * H * (W / 4);
       // both gradients requested: one block row each
       const unsigned nb = (unsigned)((threads + 255) / 256);
-      if ((g_tuning.bwd_off & 4) == 0 && (W == 8 || W == 16 || W == 32 || W == 64 || W == 128 || W == 256)) {
+      if ((st.t.bwd_off & 4) == 0 && (W == 8 || W == 16 || W == 32 || W == 64 || W == 128 || W == 256)) {
         // the other feature map's rows through LDS (kernels/backward.h: corr_bwd_lds_kernel), a block row per gradient.  Measured
         // at the five levels of cfg2 against corr_bwd_block_kernel (both gradients, us): 14.5 / 15.1 / 20.5 / 29.9 / 54.6 before
         CorrBwdLdsParams lp{p, 256 / (W / 4), cdiv(H, 256 / (W / 4))};
@@ -906,11 +930,11 @@ size_t MFN_API(deform_conv_bwd_workspace_bytes)(int N, int Cin, int H, int W, in
 }
 
 // flow mode of the backward (mfn_deform_conv_shared_bwd): the kernels of kernels/dc_backward.h read the flow field in place of an
-// offset tensor and write d/dflow in place of goffset.  Only where dc_bwd_flow_direct() says those kernels take the whole call.
+// offset tensor and write d/dflow in place of goffset.  Only where dc_bwd_flow_direct(st, ) says those kernels take the whole call.
 struct DcFlowArgs { const float *flow; float *gflow; float scale, stride; };
-static bool dc_bwd_flow_direct(const float *x, const float *w, int N, int Cin, int H, int W, int Cout, int kh, int kw, int ph, int pw,
+static bool dc_bwd_flow_direct(const Settings &st, const float *x, const float *w, int N, int Cin, int H, int W, int Cout, int kh, int kw, int ph, int pw,
                                int dh, int dw, int groups, int req_w, const void *workspace, size_t ws_bytes) {
-  if ((g_tuning.bwd_off & 2) != 0 || (g_tuning.path_generic & 2) != 0 || (g_tuning.bwd_off & 1) != 0)
+  if ((st.t.bwd_off & 2) != 0 || (st.t.path_generic & 2) != 0 || (st.t.bwd_off & 1) != 0)
     return false;
   if (N <= 0 || !dc_bwd_shared_shape(H, W, kh, kw, 1, 1, dh, dw, groups, 1) || ph != 1 || pw != 1) return false;
   if (W % 4 != 0 || Cin % 4 != 0 || !aligned(x, 16) || !aligned(w, 16) || !aligned(workspace, 16)) return false;
@@ -919,7 +943,7 @@ static bool dc_bwd_flow_direct(const float *x, const float *w, int N, int Cin, i
   (void)ws_bytes;
   return !req_w || dc_bwd_wplan(N, Cin, H, W, Cout).ok;
 }
-static int dc_bwd_run(const float *gout, const float *x, const float *offset, const float *w, float *gx,
+static int dc_bwd_run(const Settings &st, const float *gout, const float *x, const float *offset, const float *w, float *gx,
                       float *goffset, float *gw, float *gbias, int N, int Cin, int H, int W, int Cout, int kh,
                       int kw, int sh, int sw, int ph, int pw, int dh, int dw, int groups, int dg, int req_x,
                       int req_offset, int req_w, int req_bias, void *workspace, size_t ws_bytes, void *stream, const DcFlowArgs *fl) {
@@ -941,7 +965,7 @@ static int dc_bwd_run(const float *gout, const float *x, const float *offset, co
   const size_t oplane = (size_t)Ho * Wo;
   DcBwdParams p{gout, x, offset, w, gx, goffset, gw, gbias, N, Cin, H, W, Cout, Ho, Wo, kh, kw, sh, sw, ph, pw, dh, dw,
                 groups, dg, req_x, req_offset, req_w, req_bias, 1};
-  const bool w_mfma = req_w && groups == 1 && dg == 1 && (g_tuning.path_generic & 2) == 0 && kh * kw <= 25;
+  const bool w_mfma = req_w && groups == 1 && dg == 1 && (st.t.path_generic & 2) == 0 && kh * kw <= 25;
   // The weight / bias gradient in the forward's orientation (kernels/dc_backward.h: dc_bwd_weight_pc_kernel): columns produced
   // as the forward kernel does, pixels as the reduction dimension; the blocks' partial sums go through the workspace (when it
   // has the room) and are added in block order.  `zero`: write-mode gradients of the OTHER kernels of this call (gx, goffset)
@@ -989,13 +1013,13 @@ static int dc_bwd_run(const float *gout, const float *x, const float *offset, co
   }
   if (req_x || req_offset) {
     if (groups == 1 && dg == 1 && sh == 1 && sw == 1 && Ho == H && Wo == W && H < 65536 && W < 65536 && kh * kw <= 9 &&
-        (g_tuning.path_generic & 2) == 0) {
+        (st.t.path_generic & 2) == 0) {
       // fp32-MFMA column gradient + LDS-privatised scatter (kernels/backward.h: dc_bwd_input_tile_kernel)
       DcBwdIParams ip{gout, x, offset, w, gx, goffset, N, Cin, H, W, Cout, kh, kw, ph, pw, dh, dw, kh * kw,
                       cdiv(W, DCI_TW), cdiv(H, DCI_TH), req_x, req_offset,
                       (unsigned long long *)((unsigned long long)g_timeline & ~1ull)};
       if (fl) { ip.flow = fl->flow; ip.gflow = fl->gflow; ip.flow_scale = fl->scale; ip.flow_stride = fl->stride; }
-      if ((g_tuning.bwd_off & 1) == 0 && dc_bwd_shared_shape(H, W, kh, kw, sh, sw, dh, dw, groups, dg) &&
+      if ((st.t.bwd_off & 1) == 0 && dc_bwd_shared_shape(H, W, kh, kw, sh, sw, dh, dw, groups, dg) &&
           (size_t)Cout * H * W < ((size_t)1 << 29) && (size_t)Cout * Cin * 9 < ((size_t)1 << 29)) {
         // all nine taps in one pass where they share one offset per pixel (the reference's only use); tiles that do not
         // qualify are done tap by tap by the same blocks
@@ -1074,7 +1098,7 @@ int MFN_API(deform_conv_bwd)(const float *gout, const float *x, const float *off
                              float *goffset, float *gw, float *gbias, int N, int Cin, int H, int W, int Cout, int kh,
                              int kw, int sh, int sw, int ph, int pw, int dh, int dw, int groups, int dg, int req_x,
                              int req_offset, int req_w, int req_bias, void *workspace, size_t ws_bytes, void *stream) {
-  return dc_bwd_run(gout, x, offset, w, gx, goffset, gw, gbias, N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, dg, req_x,
+  return dc_bwd_run(settings_now(), gout, x, offset, w, gx, goffset, gw, gbias, N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, dg, req_x,
                     req_offset, req_w, req_bias, workspace, ws_bytes, stream, nullptr);
 }
 
@@ -1107,6 +1131,7 @@ int MFN_API(deform_conv_shared_bwd)(const float *gout, const float *x, const flo
                                     const float *w, float *gx, float *gflow, float *gw, float *gbias, int N, int Cin, int H,
                                     int W, int Cout, int kh, int kw, int ph, int pw, int dh, int dw, int groups, int req_x,
                                     int req_flow, int req_w, int req_bias, void *workspace, size_t ws_bytes, void *stream) {
+  const Settings st = settings_now();
   if (N != 0 && !flow) return fail(MFN_E_NULL, "deform_conv_shared_bwd: NULL flow");
   if (flow_stride == 0.f) return fail(MFN_E_PARAM, "deform_conv_shared_bwd: flow_stride must be non-zero");
   if (!req_ok(req_flow)) return fail(MFN_E_PARAM, "deform_conv_shared_bwd: req must be 0 (null), 1 (write) or 3 (add)");
@@ -1120,10 +1145,10 @@ int MFN_API(deform_conv_shared_bwd)(const float *gout, const float *x, const flo
     return fail(MFN_E_PARAM, "deform_conv_shared_bwd: workspace of mfn_deform_conv_shared_bwd_workspace_bytes (16-byte aligned) required");
   float *off = (float *)workspace, *goff = (float *)((char *)workspace + ob);
   void *inner = (char *)workspace + 2 * ob;
-  if (dc_bwd_flow_direct(x, w, N, Cin, H, W, Cout, kh, kw, ph, pw, dh, dw, groups, req_w, inner, ws_bytes - 2 * ob)) {
+  if (dc_bwd_flow_direct(st, x, w, N, Cin, H, W, Cout, kh, kw, ph, pw, dh, dw, groups, req_w, inner, ws_bytes - 2 * ob)) {
     // the lane = pixel kernels take the flow field itself: no offsets, no per-tap offset gradient (tuning key dc.bwdflow)
     const DcFlowArgs fl{flow, gflow, flow_scale, flow_stride};
-    return dc_bwd_run(gout, x, nullptr, w, gx, nullptr, gw, gbias, N, Cin, H, W, Cout, kh, kw, 1, 1, ph, pw, dh, dw, groups, 1, req_x,
+    return dc_bwd_run(st, gout, x, nullptr, w, gx, nullptr, gw, gbias, N, Cin, H, W, Cout, kh, kw, 1, 1, ph, pw, dh, dw, groups, 1, req_x,
                       req_flow, req_w, req_bias, inner, ws_bytes - 2 * ob, stream, &fl);
   }
   if (N != 0 && (rc = MFN_API(offsets_from_flow)(flow, off, N, H, W, kh * kw, flow_scale, flow_stride, stream))) return rc;
@@ -1168,10 +1193,10 @@ static int conv_kind(int kh, int kw, int transposed, const ConvGeo &g) {
   return 0;
 }
 // Ho / Wo: the output grid the kernel's pixel tiles cover (kind 3: the INPUT grid), Cout: its filter count (kind 3: 4x)
-static ConvPlan conv_plan(int N, int Cin, int Cout, int Ho, int Wo, int kh, int kw, int groups, int kind) {
+static ConvPlan conv_plan(const Settings &st, int N, int Cin, int Cout, int Ho, int Wo, int kh, int kw, int groups, int kind) {
   ConvPlan pl;
   memset(&pl, 0, sizeof(pl));
-  if (!kind || groups != 1 || Wo < 8 || (g_tuning.path_generic & 4)) return pl;
+  if (!kind || groups != 1 || Wo < 8 || (st.t.path_generic & 4)) return pl;
   if (kind == 3) { kh = kw = 3; }
   pl.mfma = 1;
   pl.tiles_x = (Wo + 7) / 8;
@@ -1192,10 +1217,10 @@ static ConvPlan conv_plan(int N, int Cin, int Cout, int Ho, int Wo, int kh, int 
     // conv3_2 251 -> 228 us, conv4a / 4b / 4c 31 / 44 / 42 -> 26 / 36 / 36)
     if (mt == 2 && mtiles == 3) mt = 1;
   }
-  if (g_tuning.conv_mt >= 1 && g_tuning.conv_mt <= 4 && kind != 2) mt = g_tuning.conv_mt;
-  if (g_tuning.conv_pt == 1 || g_tuning.conv_pt == 4) pt = g_tuning.conv_pt;
+  if (st.t.conv_mt >= 1 && st.t.conv_mt <= 4 && kind != 2) mt = st.t.conv_mt;
+  if (st.t.conv_pt == 1 || st.t.conv_pt == 4) pt = st.t.conv_pt;
   if (pt == 1 && mt > 2) mt = 2;
-  pl.mma = (t_arith.conv != 0 && kind != 2 && T == 9) ? 1 : 0;   // the bf16 x 3 form unless the thread asked for fp32 FMA chains
+  pl.mma = (st.conv != 0 && kind != 2 && T == 9) ? 1 : 0;   // the bf16 x 3 form unless the thread asked for fp32 FMA chains
   if (pl.mma) {   // the instantiations of the bf16 x 3 form: (1,1), (1,4), (2,4), (4,4)
     if (pt == 1) mt = 1;
     else if (mt == 3) mt = 2;
@@ -1214,12 +1239,12 @@ static ConvPlan conv_plan(int N, int Cin, int Cout, int Ho, int Wo, int kh, int 
 // Plain 3x3 / stride 1 / pad 1 / dilation 1 convolutions with whole 32-filter tiles on images of at least 384 pixel tiles (levels 2 and 3
 // of the 384x512 batch-8 network): dc_mma_kernel's CONV form.  Measured against conv_mfma_kernel's bf16 x 3 form, same boxes
 // (profiles/r05_conv_dcm.txt): level-2 decoder layers 1.2-1.6x, level 3 1.6-1.8x, level 4 (192 tiles) no gain -- left where it was.
-static bool conv_dcm_plan(ConvPlan &pl, int N, int Cin, int Cout, int H, int W) {
-  if (g_tuning.conv_dcm == 1 || t_arith.conv == 0 || (g_tuning.path_generic & 4) || g_tuning.conv_mt || g_tuning.conv_pt) return false;
+static bool conv_dcm_plan(const Settings &st, ConvPlan &pl, int N, int Cin, int Cout, int H, int W) {
+  if (st.t.conv_dcm == 1 || st.conv == 0 || (st.t.path_generic & 4) || st.t.conv_mt || st.t.conv_pt) return false;
   if (Cout < 32 || W % 4 != 0 || W < 8) return false;   // (a 16-filter layer would fill half a tile)
   const int tiles_x = (W + 7) / 8, tiles_y = (H + 3) / 4;
   const long tiles = (long)N * tiles_y * tiles_x;
-  if (tiles < 384 && g_tuning.conv_dcm != 2) return false;
+  if (tiles < 384 && st.t.conv_dcm != 2) return false;
   memset(&pl, 0, sizeof(pl));
   pl.dcm = 1;
   pl.tiles_x = tiles_x; pl.tiles_y = tiles_y; pl.ntiles = (int)tiles;
@@ -1236,7 +1261,7 @@ static bool conv_dcm_plan(ConvPlan &pl, int N, int Cin, int Cout, int H, int W) 
   }
   // few tiles and two filter tiles (level 3's 64-filter layers): three pixel tiles x four K slices, as the deformable convolution there
   if (tiles < 1024 && mt == 2 && pl.groups16 % 4 == 0) { pt = 3; kw = 4; }
-  if (g_tuning.dc_pt > 0 && kw == 1) pt = g_tuning.dc_pt;   // measurement (a build that instantiates it: MFN_DCMC_CONFIGS)
+  if (st.t.dc_pt > 0 && kw == 1) pt = st.t.dc_pt;   // measurement (a build that instantiates it: MFN_DCMC_CONFIGS)
   pl.mt = mt; pl.pt = pt; pl.kw = kw;
   pl.mgroups = (mtiles + mt - 1) / mt;
   pl.gps = pl.groups16 / kw;
@@ -1289,23 +1314,23 @@ static int conv_dims(const char *what, int N, int Cin, int H, int W, int Cout, i
 // kernel family + plan of a call; CoutK / HoK / WoK / T describe the problem the MFMA kernel sees (kind 3: the pseudo
 // 3x3 convolution on the input grid), pack_mode is conv_pack_weights_kernel's `transposed`
 struct ConvSetup { int kind, T, CoutK, HoK, WoK, pack_mode; ConvPlan pl; };
-static ConvSetup conv_setup(int N, int Cin, int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
+static ConvSetup conv_setup(const Settings &st, int N, int Cin, int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
                             int groups, int transposed, int adj_h, int adj_w, int Ho, int Wo, bool allow_dcm = true) {
   ConvSetup cs;
   const ConvGeo g{sh, sw, ph, pw, dh, dw, adj_h, adj_w};
   cs.kind = conv_kind(kh, kw, transposed, g);
   if (cs.kind >= 3) { cs.T = 9; cs.CoutK = 4 * Cout; cs.HoK = H; cs.WoK = W; cs.pack_mode = cs.kind == 3 ? 2 : 3; }
   else { cs.T = kh * kw; cs.CoutK = Cout; cs.HoK = Ho; cs.WoK = Wo; cs.pack_mode = transposed ? 1 : 0; }
-  cs.pl = conv_plan(N, Cin, cs.CoutK, cs.HoK, cs.WoK, kh, kw, groups, cs.kind);
+  cs.pl = conv_plan(st, N, Cin, cs.CoutK, cs.HoK, cs.WoK, kh, kw, groups, cs.kind);
   // the prediction heads: a channel reduction with 1-4 filters does not belong on a 32-filter matrix tile
   if (cs.kind == 1 && Cout <= 4 && groups == 1 && sh == 1 && sw == 1 && ph == 1 && pw == 1 && dh == 1 && dw == 1 && conv_few_shape_ok(W) &&
-      !(g_tuning.path_generic & 4) && g_tuning.conv_mt == 0 && g_tuning.conv_pt == 0) {
+      !(st.t.path_generic & 4) && st.t.conv_mt == 0 && st.t.conv_pt == 0) {
     memset(&cs.pl, 0, sizeof(cs.pl));
     cs.pl.few = 1;
   }
   if (allow_dcm && cs.kind == 1 && !cs.pl.few && cs.pl.mfma &&
       dcm_conv_shape_ok(N, (size_t)Cin * H * W, H, W, kh, kw, sh, sw, ph, pw, dh, dw, groups))
-    conv_dcm_plan(cs.pl, N, Cin, Cout, H, W);
+    conv_dcm_plan(st, cs.pl, N, Cin, Cout, H, W);
   if (cs.pl.dcm) cs.pl.mfma = 1;
   return cs;
 }
@@ -1314,18 +1339,19 @@ size_t MFN_API(conv2d_packed_weight_bytes)(int N, int Cin, int H, int W, int Cou
                                            int dh, int dw, int groups, int transposed) {
   int Ho, Wo;
   if (conv_dims("conv2d", N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, transposed, 0, 0, &Ho, &Wo)) return 0;
-  const ConvSetup cs = conv_setup(N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, transposed, 0, 0, Ho, Wo);
+  const ConvSetup cs = conv_setup(settings_now(), N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, transposed, 0, 0, Ho, Wo);
   if (!cs.pl.mfma) return (((size_t)Cout * (Cin / groups) * kh * kw * sizeof(float)) + 15) / 16 * 16;
   return cs.pl.wt_bytes;
 }
 size_t MFN_API(conv2d_workspace_bytes)(int N, int Cin, int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph, int pw,
                                        int dh, int dw, int groups, int transposed) {
+  const Settings st = settings_now();
   int Ho, Wo;
   if (conv_dims("conv2d", N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, transposed, 0, 0, &Ho, &Wo)) return 0;
-  const ConvSetup cs = conv_setup(N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, transposed, 0, 0, Ho, Wo);
+  const ConvSetup cs = conv_setup(st, N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, transposed, 0, 0, Ho, Wo);
   if (cs.pl.few) return conv_few_workspace_bytes(N, Cin, H, W, Cout);   // partial sums of the channel blocks (coarse levels)
   if (cs.pl.dcm) {   // a call whose tensors are not 16-byte aligned packs for conv_mfma_kernel instead: room for either
-    const ConvSetup c2 = conv_setup(N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, transposed, 0, 0, Ho, Wo, false);
+    const ConvSetup c2 = conv_setup(st, N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, transposed, 0, 0, Ho, Wo, false);
     return cs.pl.wt_bytes > c2.pl.wt_bytes ? cs.pl.wt_bytes : c2.pl.wt_bytes;
   }
   return cs.pl.mfma ? cs.pl.wt_bytes : 0;   // the re-laid-out weights of a call that is given `w` instead of a packed buffer
@@ -1339,7 +1365,7 @@ int MFN_API(conv2d_pack_weights)(const float *w, int N, int Cin, int H, int W, i
   if (rc) return rc;
   if (!w || !packed || !layout_tag) return fail(MFN_E_NULL, "conv2d_pack_weights: NULL pointer");
   if (!aligned(packed, 16)) return fail(MFN_E_ALIGN, "conv2d_pack_weights: packed buffer must be 16-byte aligned");
-  const ConvSetup cs = conv_setup(N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, transposed, 0, 0, Ho, Wo);
+  const ConvSetup cs = conv_setup(settings_now(), N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, transposed, 0, 0, Ho, Wo);
   const size_t need = MFN_API(conv2d_packed_weight_bytes)(N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, transposed);
   if (packed_bytes < need) return fail(MFN_E_WORKSPACE, "conv2d_pack_weights: %zu bytes required (got %zu)", need, packed_bytes);
   if (!cs.pl.mfma) {
@@ -1360,6 +1386,7 @@ int MFN_API(conv2d_fwd)(const float *x, long long in_batch_stride, const float *
                         int Cin, int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int groups,
                         int transposed, int adj_h, int adj_w, int activation, void *workspace, size_t workspace_bytes,
                         void *stream) {
+  const Settings st = settings_now();
   const char *what = transposed ? "conv2d_transpose_fwd" : "conv2d_fwd";
   int Ho, Wo;
   int rc = conv_dims(what, N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, transposed, adj_h, adj_w, &Ho, &Wo);
@@ -1388,12 +1415,12 @@ int MFN_API(conv2d_fwd)(const float *x, long long in_batch_stride, const float *
   // the matrix-core deformable kernel's convolution form wants 16-byte rows in both tensors and offsets below 2^32 bytes; a call that is
   // given `w` (packed here, per call) and does not qualify takes conv_mfma_kernel, one with weights PACKED for it is refused
   const bool dcm_call_ok = aligned(x, 16) && aligned(out, 16) && xnst % 4 == 0 && onst % 4 == 0 && (size_t)N * xnst < ((size_t)1 << 30);
-  ConvSetup cs = conv_setup(N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, transposed, adj_h, adj_w, Ho, Wo);
+  ConvSetup cs = conv_setup(st, N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, transposed, adj_h, adj_w, Ho, Wo);
   if (cs.pl.dcm && !dcm_call_ok) {
     if (packed_or_null)
       return fail(MFN_E_ALIGN, "%s: weights packed for the matrix-core convolution need x / out 16-byte aligned with batch strides that are multiples of 4 "
                   "(and N * in_batch_stride < 2^30)", what);
-    cs = conv_setup(N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, transposed, adj_h, adj_w, Ho, Wo, false);
+    cs = conv_setup(st, N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, transposed, adj_h, adj_w, Ho, Wo, false);
   }
   const ConvPlan &pl = cs.pl;
   if (!pl.mfma) {
@@ -1516,11 +1543,11 @@ int MFN_API(leaky_relu_bwd)(const float *gout, const float *y, float *gin, size_
 struct ConvBwdWs { size_t gpre, zoff, wflip, gxtmp, s2d, inner, total; int Ho, Wo; int via_s2d; };
 // the network's transposed convolution (4x4 / stride 2 / pad 1, no adj): its data gradient as a 3x3 convolution of the
 // pixel-unshuffled output gradient (kernels/backward.h conv_s2d_kernel) on the MFMA kernels
-static bool conv_bwd_s2d_shape(int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int transposed, int adj_h, int adj_w) {
+static bool conv_bwd_s2d_shape(const Settings &st, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int transposed, int adj_h, int adj_w) {
   return transposed && kh == 4 && kw == 4 && sh == 2 && sw == 2 && ph == 1 && pw == 1 && dh == 1 && dw == 1 && !adj_h && !adj_w &&
-         !(g_tuning.path_generic & 4);
+         !(st.t.path_generic & 4);
 }
-static int conv_bwd_ws(ConvBwdWs &q, const char *what, int N, int Cin, int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph,
+static int conv_bwd_ws(const Settings &st, ConvBwdWs &q, const char *what, int N, int Cin, int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph,
                        int pw, int dh, int dw, int groups, int transposed, int adj_h, int adj_w, int activation, int req_x) {
   memset(&q, 0, sizeof(q));
   int rc = conv_dims(what, N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, transposed, adj_h, adj_w, &q.Ho, &q.Wo);
@@ -1535,7 +1562,7 @@ static int conv_bwd_ws(ConvBwdWs &q, const char *what, int N, int Cin, int H, in
   q.gxtmp = req_x == MFN_REQ_ADD ? up(in_elems * 4) : 0;
   size_t inner = 0;
   if (transposed) {   // gx = Convolution(gpre, w): (N,Cout,Ho,Wo) -> (N,Cin,H,W)
-    q.via_s2d = conv_bwd_s2d_shape(kh, kw, sh, sw, ph, pw, dh, dw, transposed, adj_h, adj_w) ? 1 : 0;
+    q.via_s2d = conv_bwd_s2d_shape(st, kh, kw, sh, sw, ph, pw, dh, dw, transposed, adj_h, adj_w) ? 1 : 0;
     if (q.via_s2d) {
       q.s2d = up(out_elems * 4);                                  // (N, 4 Cout, H, W)
       q.wflip = up((size_t)Cin * 4 * Cout * 9 * 4);               // (Cin, 4 Cout, 3, 3)
@@ -1554,12 +1581,12 @@ static int conv_bwd_ws(ConvBwdWs &q, const char *what, int N, int Cin, int H, in
       const int ah = H - ((q.Ho - 1) * sh - 2 * ph + dh * (kh - 1) + 1), aw = W - ((q.Wo - 1) * sw - 2 * pw + dw * (kw - 1) + 1);
       int Ho2, Wo2;
       if (conv_dims(what, N, Cout, q.Ho, q.Wo, Cin, kh, kw, sh, sw, ph, pw, dh, dw, 1, 1, ah, aw, &Ho2, &Wo2) == 0) {
-        const ConvSetup cs = conv_setup(N, Cout, q.Ho, q.Wo, Cin, kh, kw, sh, sw, ph, pw, dh, dw, 1, 1, ah, aw, Ho2, Wo2);
+        const ConvSetup cs = conv_setup(st, N, Cout, q.Ho, q.Wo, Cin, kh, kw, sh, sw, ph, pw, dh, dw, 1, 1, ah, aw, Ho2, Wo2);
         inner = cs.pl.mfma ? cs.pl.wt_bytes : 0;
       }
     }
     size_t wg = MFN_API(deform_conv_bwd_workspace_bytes)(N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, 1, 1);
-    if (conv_wgrad_shape_ok(Cin, Cout, H, W, kh, kw, sh, sw, ph, pw, dh, dw) && !(g_tuning.path_generic & 4)) {
+    if (conv_wgrad_shape_ok(Cin, Cout, H, W, kh, kw, sh, sw, ph, pw, dh, dw) && !(st.t.path_generic & 4)) {
       // the convolution's own weight-gradient kernel (conv_wgrad.h) -- taken only when gpre and x are 16-byte aligned as well, which
       // the size query cannot know: an offset view of x falls back to the deformable kernels, so the scratch serves either path
       size_t slab = conv_wgrad_plan(N, Cin, Cout, H, W).slab_bytes;
@@ -1576,7 +1603,7 @@ static int conv_bwd_ws(ConvBwdWs &q, const char *what, int N, int Cin, int H, in
 size_t MFN_API(conv2d_bwd_workspace_bytes)(int N, int Cin, int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph, int pw,
                                            int dh, int dw, int groups, int transposed, int adj_h, int adj_w, int activation) {
   ConvBwdWs q;
-  if (N <= 0 || conv_bwd_ws(q, "conv2d_bwd_workspace_bytes", N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, transposed,
+  if (N <= 0 || conv_bwd_ws(settings_now(), q, "conv2d_bwd_workspace_bytes", N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, transposed,
                             adj_h, adj_w, activation, MFN_REQ_ADD))
     return 0;
   return q.total;
@@ -1594,12 +1621,13 @@ int MFN_API(conv2d_bwd)(const float *gout, const float *x, const float *w, const
                         float *gbias, int N, int Cin, int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph, int pw,
                         int dh, int dw, int groups, int transposed, int adj_h, int adj_w, int activation, int req_x, int req_w,
                         int req_bias, void *workspace, size_t ws_bytes, void *stream) {
+  const Settings st = settings_now();
   const char *what = transposed ? "conv2d_transpose_bwd" : "conv2d_bwd";
   if (!req_ok(req_x) || !req_ok(req_w) || !req_ok(req_bias)) return fail(MFN_E_PARAM, "%s: req must be 0 (null), 1 (write) or 3 (add)", what);
   if (groups != 1) return fail(MFN_E_UNSUPPORTED, "%s: num_group=%d (the reference's blocks use 1)", what, groups);
   if (activation != MFN_ACT_NONE && activation != MFN_ACT_LEAKY_0_1) return fail(MFN_E_PARAM, "%s: unknown activation %d", what, activation);
   ConvBwdWs q;
-  int rc = conv_bwd_ws(q, what, N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, transposed, adj_h, adj_w, activation, req_x);
+  int rc = conv_bwd_ws(st, q, what, N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, transposed, adj_h, adj_w, activation, req_x);
   if (rc) return rc;
   if (!w || (N != 0 && (!gout || !x))) return fail(MFN_E_NULL, "%s: NULL tensor pointer", what);
   if (activation == MFN_ACT_LEAKY_0_1 && N != 0 && !y_or_null) return fail(MFN_E_NULL, "%s: the forward output is needed for the fused LeakyReLU", what);
@@ -1653,9 +1681,9 @@ int MFN_API(conv2d_bwd)(const float *gout, const float *x, const float *w, const
     if (rc) return rc;
     if (req_x == MFN_REQ_ADD && (rc = accumulate_launch(gx, gxtmp, in_elems, s))) return hipfail(rc, what);
   }
-  if (req_w && !transposed && conv_wgrad_shape_ok(Cin, Cout, H, W, kh, kw, sh, sw, ph, pw, dh, dw) && !(g_tuning.path_generic & 4) &&
+  if (req_w && !transposed && conv_wgrad_shape_ok(Cin, Cout, H, W, kh, kw, sh, sw, ph, pw, dh, dw) && !(st.t.path_generic & 4) &&
       aligned(gpre, 16) && aligned(x, 16)) {
-    if ((rc = conv_wgrad_launch(gpre, x, gw, inner, N, Cin, Cout, H, W, dh, req_w == MFN_REQ_ADD ? 1 : 0, s, t_arith.conv != 0))) return hipfail(rc, what);
+    if ((rc = conv_wgrad_launch(gpre, x, gw, inner, N, Cin, Cout, H, W, dh, req_w == MFN_REQ_ADD ? 1 : 0, s, st.conv != 0))) return hipfail(rc, what);
   } else if (req_w) {
     const size_t wplane = transposed ? (size_t)H * W : (size_t)Ho * Wo;
     if ((rc = fill_zero_launch(zoff, (size_t)N * 2 * kh * kw * wplane, s))) return hipfail(rc, what);

@@ -350,16 +350,46 @@ inline int corr_tiled_launch(CorrParams p, hipStream_t stream, const char *name)
                 corr_tiled_lds_bytes<D, TW, NCH, CK>(), stream, p);
 }
 
+// ---- the forms of the correlation forward ------------------------------------------------------------
+// The one place where the public values of corr.variant / corr.form (tuning.h) are given their meaning: a kernel family and the
+// point of that family's template parameters.  Plans (api_impl.inc corr_plan) and launch switches take a CorrForm, never the integer;
+// a value this table does not list names no kernel: the library chooses.
+enum class CorrFamily { Generic, Direct, Tiled, Dma, Gram, GramK };
+struct CorrForm {
+  int code;            // the public value
+  CorrFamily family;
+  int groups;          // Tiled / Dma: channel groups inside a block (1: channels are split over blockIdx.y slices instead)
+  int row_pairs;       // Dma: displacement-row pairs per block, the rest of a tile's rows over blockIdx.z (0 = all in one block)
+  int terms;           // Gram: TERMS of corr_gram_kernel -- 5 three bf16 terms split on the matrix cores, 1 raw fp32 operands
+  int f2_rows;         // GramK: f2 rows per block (0 = half of the window)
+};
+enum CorrFormId { kCorrTiled, kCorrDma1, kCorrDma2, kCorrDma3, kCorrDmaRows1, kCorrDmaRows2, kCorrGramK2, kCorrGramKHalf, kCorrGramF32,
+                  kCorrGramBf16, kCorrFormCount };
+constexpr CorrForm kCorrForms[kCorrFormCount] = {
+    {6, CorrFamily::Tiled, 1, 0, 0, 0},   // corr_tiled_kernel: images narrower than 32 columns
+    {16, CorrFamily::Dma, 1, 0, 0, 0},    // corr_dma_kernel, level 2: every block of the launch resident
+    {20, CorrFamily::Dma, 2, 0, 0, 0},    // two channel groups
+    {22, CorrFamily::Dma, 3, 0, 0, 0},    // three channel groups (86..127 tiles: one 15-wave block per tile)
+    {26, CorrFamily::Dma, 4, 1, 0, 0},    // one row pair per block (blockIdx.z), 4 channel groups
+    {31, CorrFamily::Dma, 2, 2, 0, 0},    // two row pairs per block, 2 channel groups
+    {44, CorrFamily::GramK, 0, 0, 0, 2},  // corr_gramk_kernel: two f2 rows per block (5 / 3 blocks per f1 block for md = 4 / 2)
+    {45, CorrFamily::GramK, 0, 0, 0, 0},  // ... half the window per block
+    {46, CorrFamily::Gram, 0, 0, 1, 0},   // corr_gram_kernel on the fp32 matrix instruction
+    {48, CorrFamily::Gram, 0, 0, 5, 0},   // ... on the bf16 matrix cores (64-channel levels: two channel chunks)
+};
+inline const CorrForm *corr_form(int code) {
+  for (const CorrForm &f : kCorrForms)
+    if (f.code == code) return &f;
+  return nullptr;
+}
+
 // The one point of (NCH, CK, DYW, PF, WPE) that is still built: one displacement row per wave, one 4-px chunk per lane,
 // 4-channel stages, no register prefetch, >= 4 waves per SIMD -- the kernel of images narrower than 32 columns
 // (corr.variant 6).  Rounds 1 / 2 swept eight points and a half-wave form (corr_hw_kernel); none of them is selected by a plan.
-constexpr int kCorrVariants = 48;  // valid values of corr.variant: 6 (corr_tiled_kernel), 16 / 20 / 22 / 26 / 31 (corr_dma_kernel), 40 / 41 / 42 / 43 (corr_gram_kernel), 44 / 45 (corr_gramk_kernel)
-inline bool corr_variant_known(int v) { return v == 6 || v == 16 || v == 20 || v == 22 || v == 26 || v == 31 || (v >= 40 && v <= 48); }
 template <int D, int TW>
-inline int corr_tiled_variant(const CorrParams &p, int /*variant*/, hipStream_t s) {
+inline int corr_tiled_form(const CorrParams &p, hipStream_t s) {
   return corr_tiled_launch<D, TW, 1, 4, 1, false, 4>(p, s, "corr_tiled_v6");
 }
-inline int corr_variant_tile_h(int tw, int variant) { return variant >= 8 ? 4 : (256 / tw); }
 
 #ifndef MFN_CORR_ABLATE
 #define MFN_CORR_ABLATE 0  // tools/corr_ablate_build.py: 1 no LDS operand reads, 2 no FMAs (single-buffered consume only)
@@ -688,14 +718,12 @@ inline int corr_dma_launch(CorrParams p, hipStream_t stream, const char *name) {
 // them (api_impl.inc corr_plan: >= 400 tiles / 128-399 / fewer).  Rounds 1 / 2 measured sixteen more points (deeper rings,
 // 8- and 16-channel stages, operand double buffering at level 2, staggered block starts): DESIGN.md 4.1.
 template <int D>
-inline int corr_dma_variant(const CorrParams &p, int variant, hipStream_t s) {
-  switch (variant) {
-    case 20: return corr_dma_launch<D, 8, 2, 2, true, 2>(p, s, "corr_dma_v20");   // two channel groups
-    case 22: return corr_dma_launch<D, 8, 2, 1, true, 3>(p, s, "corr_dma_v22");   // three channel groups (86..127 tiles: one 15-wave block per tile)
-    case 26: return corr_dma_launch<D, 4, 2, 2, true, 4, 1>(p, s, "corr_dma_v26");  // one row pair per block (blockIdx.z), 4 channel groups
-    case 31: return corr_dma_launch<D, 4, 2, 2, true, 2, 2>(p, s, "corr_dma_v31");  // two row pairs per block, 2 channel groups
-    default: return corr_dma_launch<D, 4, 2, 5, false>(p, s, "corr_dma_v16");     // level 2: every block of the launch resident
-  }
+inline int corr_dma_form(const CorrParams &p, const CorrForm &f, hipStream_t s) {
+  if (f.groups == 2 && !f.row_pairs) return corr_dma_launch<D, 8, 2, 2, true, 2>(p, s, "corr_dma_v20");
+  if (f.groups == 3) return corr_dma_launch<D, 8, 2, 1, true, 3>(p, s, "corr_dma_v22");
+  if (f.row_pairs == 1) return corr_dma_launch<D, 4, 2, 2, true, 4, 1>(p, s, "corr_dma_v26");
+  if (f.row_pairs == 2) return corr_dma_launch<D, 4, 2, 2, true, 2, 2>(p, s, "corr_dma_v31");
+  return corr_dma_launch<D, 4, 2, 5, false>(p, s, "corr_dma_v16");
 }
 
 // ---- slice reduction: out = (sum_s partial[s]) / C, slices summed in index order ------------------

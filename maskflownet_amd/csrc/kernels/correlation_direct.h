@@ -112,6 +112,8 @@ __global__ __launch_bounds__(1024) void corr_direct_kernel(CorrDirectParams p) {
                     v[3], p.st_policy);
 }
 
+// one band row of one channel slice fits a block of 1024 threads (corr_direct_launch finds a band height)
+inline bool corr_direct_shape_ok(int W, int D) { return (W / 4) * D <= 1024; }
 // plan: the band height R that gives the most channel slices within 1024 threads (latency is what counts here)
 template <int D>
 inline int corr_direct_launch(CorrDirectParams p, hipStream_t stream) {

@@ -39,6 +39,7 @@
 #pragma once
 #include "../mfn_rt.h"
 #include "msplit.h"
+#include "correlation.h"
 
 // measurement builds only (tools/gram_ablate_build.py): bit 1 no matrix instructions / de-skew / stores (DMA, LDS reads and
 // conversions remain), 2 no stores, 4 no conversions (operands are the raw bits), 8 no DMA (the ring is never filled)
@@ -692,7 +693,6 @@ inline int corr_gram_launch(CorrGramParams p, hipStream_t stream, const char *na
   return launch(name, corr_gram_kernel<D, T, NSLOT, NWV, TERMS, POL, LEAKY, SP, COOP, NC>, dim3((unsigned)nblk), dim3(NWV * 64), lds, stream, p);
 }
 
-inline bool corr_variant_gram(int v) { return v == 46 || v == 48; }
 // the launch's index range (corr_gram_launch: block id x divisor below 2^32 for the magic divisions): images of a million rows do not
 // take this kernel -- the plan asks before it picks it, so that such a call runs on another kernel instead of failing
 inline bool corr_gram_range_ok(int N, int H, int W, int rows) {
@@ -709,13 +709,12 @@ inline int corr_gram_rows(int /*N*/, int H, int /*W*/, int override_rows, int C 
   if (override_rows == 6 || override_rows == 8) return override_rows;
   return (H % 6 != 0 && H % 8 == 0) ? 8 : 6;
 }
-// corr.variant 40: three terms, six products, cooperative stores (full lines through LDS, written through unless the caller's
-// policy says plain), a ring of 4 tiles.  The measured-and-lost forms of round 4 -- 41 (two terms, ~1e-5 relative), 42 (every
-// wave stores its own 32-byte runs: 13.2 us against 10.45), 43 (two waves per item) -- are no longer instantiated in the shipped
-// library; the template parameters that selected them (TERMS, SP, COOP) remain, profiles/r04_corr_gram_experiments.md
-// holds their numbers.
+// corr.variant 48 / 46 (correlation.h kCorrForms: terms = 5 / 1): cooperative stores (full lines through LDS, written through unless the
+// caller's policy says plain), a ring of 4 tiles.  The measured-and-lost forms of round 4 (two terms, every wave storing its own
+// 32-byte runs, two waves per item) are no longer instantiated in the shipped library; the template parameters
+// that selected them (TERMS, SP, COOP) remain, profiles/r04_corr_gram_experiments.md holds their numbers.
 template <int D>
-inline int corr_gram_variant(const CorrGramParams &p, int variant, hipStream_t s) {
+inline int corr_gram_form(const CorrGramParams &p, const CorrForm &f, hipStream_t s) {
   const bool wt = (p.store_policy & 2) != 0;
 #define MFN_GRAM_(TT_, TERMS_, NAME_) \
   (p.leaky ? (wt ? corr_gram_launch<D, TT_, 4, 4, TERMS_, 2, true, 1, true>(p, s, NAME_) : corr_gram_launch<D, TT_, 4, 4, TERMS_, 0, true, 1, true>(p, s, NAME_)) \
@@ -727,7 +726,7 @@ inline int corr_gram_variant(const CorrGramParams &p, int variant, hipStream_t s
     return MFN_GRAM2_(1);   // 2-row items (4-row items tie, 6-row items lose: profiles/r06_corr_l3.txt)
 #undef MFN_GRAM2_
   }
-  if (variant == 46) return p.rows == 8 ? MFN_GRAM_(4, 1, "corr_gram_v46") : MFN_GRAM_(3, 1, "corr_gram_v46");
+  if (f.terms == 1) return p.rows == 8 ? MFN_GRAM_(4, 1, "corr_gram_v46") : MFN_GRAM_(3, 1, "corr_gram_v46");
   return p.rows == 8 ? MFN_GRAM_(4, 5, "corr_gram_v48") : MFN_GRAM_(3, 5, "corr_gram_v48");
 #undef MFN_GRAM_
 }

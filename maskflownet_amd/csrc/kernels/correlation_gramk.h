@@ -160,12 +160,6 @@ __global__ __launch_bounds__(NW * 64) void corr_gramk_kernel(CorrGramKParams p) 
   }
 }
 
-inline bool corr_variant_gramk(int v) { return v == 44 || v == 45; }
-// f2 rows per block: 44 = two (5 / 3 blocks per f1 block for md = 4 / 2), 45 = half the window
-inline int corr_gramk_rg(int variant, int D) {
-  if (D == 9) return variant == 44 ? 2 : 5;
-  return variant == 44 ? 2 : 3;
-}
 inline bool corr_gramk_shape_ok(int C, int W) { return W % 8 == 0 && C >= 1 && C <= 256; }
 
 template <int D, int NW, int RG>
@@ -192,9 +186,9 @@ inline int corr_gramk_nw(const CorrGramKParams &p, hipStream_t s) {
   }
 }
 template <int D>
-inline int corr_gramk_variant(const CorrGramKParams &p, int variant, hipStream_t s) {
+inline int corr_gramk_form(const CorrGramKParams &p, const CorrForm &f, hipStream_t s) {
   constexpr int S = D + 1;
-  if (variant == 44) return corr_gramk_nw<D, 2>(p, s);
+  if (f.f2_rows == 2) return corr_gramk_nw<D, 2>(p, s);
   return corr_gramk_nw<D, S / 2>(p, s);
 }
 

@@ -5,8 +5,8 @@
 // between -- DESIGN.md records what each of them measured.  Round 5: the three keys that selected ARITHMETIC (corr.gram, dc.mma,
 // conv.mma) are gone from here: that is mfn_set_arithmetic (include/mfn_hip.h), per thread; these keys only choose tilings / paths.
 //   corr.variant  6: corr_tiled_kernel (images narrower than 16 columns), 16 / 20 / 22: corr_dma_kernel with 1 / 2 / 3 channel
-//                 groups, 26 / 31: the same with a tile's displacement rows spread over 5 / 3 blocks (coarse levels); -1 = the
-//                 plan (api_impl.inc corr_plan)
+//                 groups, 26 / 31: the same with a tile's displacement rows spread over 5 / 3 blocks (coarse levels); -1 (or any
+//                 value kernels/correlation.h kCorrForms does not list) = the plan (api_impl.inc corr_plan)
 //                 48 / 46: corr_gram_kernel (32-channel levels, 48 also 64-channel ones: the band of the Gram matrix on the matrix cores) -- 48
 //                 the plan's form (three bf16 terms split ON the matrix cores, results leaving one step behind the chains), 46 raw operands
 //                 on the fp32 matrix instruction (an fmaf chain over the channels: the plan's form under MFN_ARITH_FP32)

@@ -16,9 +16,7 @@ using std::min;
 
 #include "../../maskflownet_amd/csrc/api_impl.inc"
 
-// the kernels the calls since the last query dispatched to, "name;name;..." (cleared by the query): which path a call took
-extern "C" int mfn_emu_test_launch_log(char *buf, int cap) {
-  std::string &log = hipemu::launch_log();
+static int take_log(std::string &log, char *buf, int cap) {
   const int n = (int)log.size();
   if (buf && cap > 0) {
     const int m = n < cap - 1 ? n : cap - 1;
@@ -28,3 +26,8 @@ extern "C" int mfn_emu_test_launch_log(char *buf, int cap) {
   log.clear();
   return n;
 }
+// the kernels the calls since the last query dispatched to, "name;name;..." (cleared by the query): which path a call took
+extern "C" int mfn_emu_test_launch_log(char *buf, int cap) { return take_log(hipemu::launch_log(), buf, cap); }
+// dry run: while on, a launch is recorded as "name gx gy gz bx by bz shared_bytes;" and its body does not run
+extern "C" void mfn_emu_test_dry_run(int on) { hipemu::dry_run() = on != 0; }
+extern "C" int mfn_emu_test_dry_log(char *buf, int cap) { return take_log(hipemu::dry_log(), buf, cap); }

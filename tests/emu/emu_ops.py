@@ -85,11 +85,25 @@ def set_tuning(**kw):
             ops.check(ops.ns.set_tuning(k.replace("_", ".", 1).encode(), int(v)))
 
 
-def launch_log():
-    """Names of the kernels launched since the last call, "name;name;..." (which path a call dispatched to)."""
-    ops = emu_ops()
-    fn = ops.ns._cdll.mfn_emu_test_launch_log
+def _take_log(symbol):
+    fn = getattr(emu_ops().ns._cdll, symbol)
     fn.restype, fn.argtypes = ctypes.c_int, [ctypes.c_char_p, ctypes.c_int]
     buf = ctypes.create_string_buffer(1 << 16)
     fn(buf, len(buf))
     return buf.value.decode()
+
+
+def launch_log():
+    """Names of the kernels launched since the last call, "name;name;..." (which path a call dispatched to)."""
+    return _take_log("mfn_emu_test_launch_log")
+
+
+def dry_run(on):
+    """While on, a launch is only recorded (dry_launches()); no kernel body runs, so buffers may be uninitialised."""
+    emu_ops().ns._cdll.mfn_emu_test_dry_run(int(bool(on)))
+
+
+def dry_launches():
+    """Launches recorded since the last call while dry_run was on: [[name, gx, gy, gz, bx, by, bz, shared_bytes], ...]."""
+    recs = [r.split(" ") for r in _take_log("mfn_emu_test_dry_log").split(";") if r]
+    return [[r[0]] + [int(v) for v in r[1:]] for r in recs]

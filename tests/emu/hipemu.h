@@ -87,11 +87,22 @@ inline Wave &wave() { return *t_block->waves[t_wave]; }
 
 // names of the kernels launched since the last query (emu_api.cpp: mfn_emu_test_launch_log)
 inline std::string &launch_log() { static std::string log; return log; }
-inline void note_launch(const char *name) { launch_log() += name; launch_log() += ';'; }
+// dry run (emu_api.cpp: mfn_emu_test_dry_run): launch() records "name gx gy gz bx by bz shared;" and skips the body, so that the
+// dispatch of shapes far too large to emulate can still be read (tests/test_dispatch_table.py)
+inline bool &dry_run() { static bool on = false; return on; }
+inline std::string &dry_log() { static std::string log; return log; }
+inline const char *&last_name() { static const char *name = "?"; return name; }
+inline void note_launch(const char *name) { launch_log() += name; launch_log() += ';'; last_name() = name; }
 
 template <class F>
 void launch(dim3 grid, dim3 block, size_t shmem, F &&body) {
   const unsigned nthreads = block.x * block.y * block.z;
+  if (dry_run()) {
+    char rec[192];
+    snprintf(rec, sizeof(rec), "%s %u %u %u %u %u %u %zu;", last_name(), grid.x, grid.y, grid.z, block.x, block.y, block.z, shmem);
+    dry_log() += rec;
+    return;
+  }
   if (nthreads % 64 != 0) {
     fprintf(stderr, "hipemu: block size %u is not a multiple of 64\n", nthreads);
     abort();

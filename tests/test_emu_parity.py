@@ -103,6 +103,11 @@ def test_correlation_gram_falls_back_off_its_shapes(ops, oracle):
     emu_ops.launch_log()
     pc.case_correlation(ops, oracle, ident, ident, (1, 12, 6, 40), 4)
     assert "corr_gram" not in emu_ops.launch_log()
+    # 40 .. 43 and 47 named forms of the Gram band that are gone: the library chooses, and the log names the kernel that ran
+    for variant in (-1, 40, 41, 42, 43, 47):
+        emu_ops.set_tuning(corr_variant=variant, corr_direct=2)
+        pc.case_correlation(ops, oracle, ident, ident, (1, 12, 6, 40), 4)
+        assert emu_ops.launch_log() == "corr_dma_v26;", variant
 
 
 @pytest.mark.parametrize("shape", [(1, 9, 18, 20), (1, 3, 6, 8), (2, 5, 9, 28)])

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-block timeline of the Gram-band correlation (corr.variant 40 / 41) at level 2: wall-clock stamps of wave 0 of every block
+"""Per-block timeline of the Gram-band correlation (corr.form 48 / 46) at level 2: wall-clock stamps of wave 0 of every block
 (start / first tiles landed / half of the steps done / end) and the same in shader cycles.
 
     python tools/timeline_build.py
@@ -15,7 +15,7 @@ import numpy as np, torch
 from maskflownet_amd import _lib, hotpath
 lib = _lib.lib()
 cfg = sys.argv[1] if len(sys.argv) > 1 else "cfg2"
-variant = int(sys.argv[2]) if len(sys.argv) > 2 else 40
+variant = int(sys.argv[2]) if len(sys.argv) > 2 else 48
 rows = int(sys.argv[3]) if len(sys.argv) > 3 else 0
 inpass = len(sys.argv) > 4 and sys.argv[4] == "inpass"   # the stamped launch follows the pass's other kernels (cold code, the previous kernel's dirty lines)
 _lib.set_tuning(corr_form=variant, corr_rows=rows)
