@@ -561,15 +561,18 @@ size_t MFN_API(deform_conv_workspace_bytes)(int N, int Cin, int H, int W, int Co
   return need;
 }
 
-size_t MFN_API(deform_conv_packed_weight_bytes)(int N, int Cin, int H, int W, int Cout, int kh, int kw, int sh, int sw,
-                                                int ph, int pw, int dh, int dw, int groups, int deform_groups) {
-  const Settings st = settings_now();
+static size_t dc_packed_bytes(const Settings &st, int N, int Cin, int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph, int pw,
+                              int dh, int dw, int groups, int deform_groups) {
   int Ho, Wo;
   if (N <= 0 || Cin <= 0 || Cout <= 0 || groups < 1 || Cin % groups ||
       MFN_API(deform_conv_out_shape)(H, W, kh, kw, sh, sw, ph, pw, dh, dw, &Ho, &Wo))
     return 0;
   if (!dc_mfma_ok(st, kh, kw, groups, deform_groups)) return (size_t)Cout * (Cin / groups) * kh * kw * sizeof(float);
   return dc_plan(st, Cin, Cout, N, Ho, Wo, dc_mma_shape(N, Cin, H, W, kh, kw, sh, sw, ph, pw, dh, dw, groups, deform_groups)).wt_bytes;
+}
+size_t MFN_API(deform_conv_packed_weight_bytes)(int N, int Cin, int H, int W, int Cout, int kh, int kw, int sh, int sw,
+                                                int ph, int pw, int dh, int dw, int groups, int deform_groups) {
+  return dc_packed_bytes(settings_now(), N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, deform_groups);
 }
 
 int MFN_API(deform_conv_pack_weights)(const float *w, int N, int Cin, int H, int W, int Cout, int kh, int kw, int sh,
@@ -578,7 +581,7 @@ int MFN_API(deform_conv_pack_weights)(const float *w, int N, int Cin, int H, int
                                       void *stream) {
   const Settings st = settings_now();
   if (!w || !packed || !layout_tag) return fail(MFN_E_NULL, "deform_conv_pack_weights: NULL pointer");
-  const size_t need = MFN_API(deform_conv_packed_weight_bytes)(N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, deform_groups);
+  const size_t need = dc_packed_bytes(st, N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, deform_groups);
   if (!need) return fail(MFN_E_SHAPE, "deform_conv_pack_weights: bad shape");
   if (packed_bytes < need) return fail(MFN_E_WORKSPACE, "deform_conv_pack_weights: %zu bytes required (got %zu)", need, packed_bytes);
   if (!aligned(packed, 16)) return fail(MFN_E_ALIGN, "deform_conv_pack_weights: packed buffer must be 16-byte aligned");
@@ -790,13 +793,17 @@ int MFN_API(deform_conv_matching_fwd)(const float *x, const float *flow, float f
                           kw, ph, pw, dh, dw, groups, workspace, ws_bytes, stream);
 }
 
+static int offsets_from_flow_run(const Settings &st, const float *flow, float *offset, int N, int H, int W, int taps, float scale, float stride,
+                                 hipStream_t s) {
+  OffsetsParams p{flow, offset, N, H, W, taps, scale, stride, store_policy_for(st, (size_t)N * 2 * taps * H * W * 4, 2, -1)};
+  return hipfail(offsets_from_flow_launch(p, s), "offsets_from_flow");
+}
 int MFN_API(offsets_from_flow)(const float *flow, float *offset, int N, int H, int W, int taps, float scale,
                                float stride, void *stream) {
   if (N != 0 && (!flow || !offset)) return fail(MFN_E_NULL, "offsets_from_flow: NULL tensor pointer");
   if (N < 0 || H <= 0 || W <= 0 || taps < 1) return fail(MFN_E_SHAPE, "offsets_from_flow: bad shape");
   if (stride == 0.f) return fail(MFN_E_PARAM, "offsets_from_flow: stride must be non-zero");
-  OffsetsParams p{flow, offset, N, H, W, taps, scale, stride, store_policy_for(settings_now(), (size_t)N * 2 * taps * H * W * 4, 2, -1)};
-  return hipfail(offsets_from_flow_launch(p, (hipStream_t)stream), "offsets_from_flow");
+  return offsets_from_flow_run(settings_now(), flow, offset, N, H, W, taps, scale, stride, (hipStream_t)stream);
 }
 
 int MFN_API(upsample_fwd)(const float *x, float *out, int N, int C, int H, int W, int factor, void *stream) {
@@ -813,6 +820,33 @@ int MFN_API(upsample_fwd)(const float *x, float *out, int N, int C, int H, int W
 // ---- backward (SURVEY.md 8 a7) -------------------------------------------------------------------------------
 static bool req_ok(int r) { return r == MFN_REQ_NULL || r == MFN_REQ_WRITE || r == MFN_REQ_ADD; }
 
+// What corr_bwd_plan decides for a backward call and mfn_correlation_bwd launches (a new kernel family: a member here, a case there).
+enum class CorrBwdFamily { Lds, Block, Gather, Scatter };
+struct CorrBwdPlan { CorrBwdFamily family; dim3 grid; int rows; size_t lds_bytes; int store_policy; };
+// aligned16: gout, both feature maps and the requested gradients allow 16-byte accesses; out_elems: elements of gout
+static CorrBwdPlan corr_bwd_plan(const Settings &st, int N, int C, int H, int W, int md, int kernel, int s1, int s2, int pad, int is_multiply,
+                                 int req1, int req2, bool aligned16, size_t out_elems) {
+  const size_t in_elems = (size_t)N * C * H * W;
+  const int D = 2 * (md / s2) + 1, cq = (C + 3) / 4;
+  const unsigned parts = (req1 && req2) ? 2u : 1u;   // both gradients requested: one block row each
+  CorrBwdPlan pl{CorrBwdFamily::Scatter, dim3((unsigned)((out_elems + 255) / 256)), 0, 0, store_policy_for(st, in_elems * 4, 2, -1)};
+  if (kernel != 1 || s1 != 1 || s2 != 1 || pad != md || !is_multiply) return pl;
+  pl.family = CorrBwdFamily::Gather;
+  pl.grid = dim3((unsigned)((in_elems + 255) / 256));
+  if (W % 4 != 0 || (D != 9 && D != 5) || !aligned16) return pl;
+  pl.family = CorrBwdFamily::Block;
+  pl.grid = dim3((unsigned)(((size_t)N * cq * H * (W / 4) + 255) / 256), parts);
+  if ((st.t.bwd_off & 4) == 0 && (W == 8 || W == 16 || W == 32 || W == 64 || W == 128 || W == 256)) {
+    // the other feature map's rows through LDS (kernels/backward.h: corr_bwd_lds_kernel), a block row per gradient.  Measured
+    // at the five levels of cfg2 against corr_bwd_block_kernel (both gradients, us): 14.5 / 15.1 / 20.5 / 29.9 / 54.6 before
+    pl.family = CorrBwdFamily::Lds;
+    pl.rows = 256 / (W / 4);
+    pl.grid = dim3((unsigned)(N * cq * cdiv(H, pl.rows)), parts);
+    pl.lds_bytes = corr_bwd_lds_bytes(H, W, D / 2);
+  }
+  return pl;
+}
+
 int MFN_API(correlation_bwd)(const float *gout, const float *d1, const float *d2, float *g1, float *g2, int N, int C,
                              int H, int W, int md, int kernel, int s1, int s2, int pad, int is_multiply, int req1,
                              int req2, void *stream) {
@@ -827,36 +861,27 @@ int MFN_API(correlation_bwd)(const float *gout, const float *d1, const float *d2
   if (N == 0 || (!req1 && !req2)) return 0;
   hipStream_t s = (hipStream_t)stream;
   const int r = md / s2, D = 2 * r + 1;
-  const size_t in_elems = (size_t)N * C * H * W;
-  if (kernel == 1 && s1 == 1 && s2 == 1 && pad == md && is_multiply) {
-    CorrBwdParams p{gout, d1, d2, g1, g2, N, C, H, W, md, D, req1, req2, store_policy_for(st, (size_t)N * C * H * W * 4, 2, -1)};
-    const bool al16 = aligned(gout, 16) && aligned(d1, 16) && aligned(d2, 16) && (!g1 || aligned(g1, 16)) && (!g2 || aligned(g2, 16));
-    if (W % 4 == 0 && (D == 9 || D == 5) && al16) {
-      const size_t threads = (size_t)N * ((C + 3) / 4) * H * (W / 4);
-      // both gradients requested: one block row each
-      const unsigned nb = (unsigned)((threads + 255) / 256);
-      if ((st.t.bwd_off & 4) == 0 && (W == 8 || W == 16 || W == 32 || W == 64 || W == 128 || W == 256)) {
-        // the other feature map's rows through LDS (kernels/backward.h: corr_bwd_lds_kernel), a block row per gradient.  Measured
-        // at the five levels of cfg2 against corr_bwd_block_kernel (both gradients, us): 14.5 / 15.1 / 20.5 / 29.9 / 54.6 before
-        CorrBwdLdsParams lp{p, 256 / (W / 4), cdiv(H, 256 / (W / 4))};
-        const dim3 grid((unsigned)(N * ((C + 3) / 4) * lp.row_blocks), (req1 && req2) ? 2u : 1u);
-        return hipfail(D == 9 ? launch("corr_bwd_lds", corr_bwd_lds_kernel<4>, grid, dim3(256), corr_bwd_lds_bytes(H, W, 4), s, lp)
-                              : launch("corr_bwd_lds", corr_bwd_lds_kernel<2>, grid, dim3(256), corr_bwd_lds_bytes(H, W, 2), s, lp),
-                       "correlation_bwd");
-      }
-      const unsigned parts = (req1 && req2) ? 2u : 1u;
-      return hipfail(launch("corr_bwd_block", corr_bwd_block_kernel<0>, dim3(nb, parts), dim3(256), 0, s, p),
-                     "correlation_bwd");
+  const bool al16 = aligned(gout, 16) && aligned(d1, 16) && aligned(d2, 16) && (!g1 || aligned(g1, 16)) && (!g2 || aligned(g2, 16));
+  const CorrBwdPlan pl = corr_bwd_plan(st, N, C, H, W, md, kernel, s1, s2, pad, is_multiply, req1, req2, al16, (size_t)N * tc * th * tw);
+  const CorrBwdParams p{gout, d1, d2, g1, g2, N, C, H, W, md, D, req1, req2, pl.store_policy};
+  switch (pl.family) {
+    case CorrBwdFamily::Lds: {
+      const CorrBwdLdsParams lp{p, pl.rows, cdiv(H, pl.rows)};
+      rc = D == 9 ? launch("corr_bwd_lds", corr_bwd_lds_kernel<4>, pl.grid, dim3(256), pl.lds_bytes, s, lp)
+                  : launch("corr_bwd_lds", corr_bwd_lds_kernel<2>, pl.grid, dim3(256), pl.lds_bytes, s, lp);
+      break;
     }
-    return hipfail(launch("corr_bwd_gather", corr_bwd_gather_kernel, dim3((unsigned)((in_elems + 255) / 256)), dim3(256), 0, s, p),
-                   "correlation_bwd");
+    case CorrBwdFamily::Block: rc = launch("corr_bwd_block", corr_bwd_block_kernel<0>, pl.grid, dim3(256), 0, s, p); break;
+    case CorrBwdFamily::Gather: rc = launch("corr_bwd_gather", corr_bwd_gather_kernel, pl.grid, dim3(256), 0, s, p); break;
+    case CorrBwdFamily::Scatter: {
+      const size_t in_elems = (size_t)N * C * H * W;
+      if (req1 == MFN_REQ_WRITE && (rc = fill_zero_launch(g1, in_elems, s))) break;
+      if (req2 == MFN_REQ_WRITE && (rc = fill_zero_launch(g2, in_elems, s))) break;
+      const CorrBwdGenericParams gp{gout, d1, d2, g1, g2, N, C, H, W, md, kernel, s1, s2, pad, is_multiply ? 1 : 0, tc, th, tw, r, D, req1, req2};
+      rc = launch("corr_bwd_scatter", corr_bwd_scatter_kernel, pl.grid, dim3(256), 0, s, gp);
+    }
   }
-  if (req1 == MFN_REQ_WRITE && (rc = fill_zero_launch(g1, in_elems, s))) return hipfail(rc, "correlation_bwd");
-  if (req2 == MFN_REQ_WRITE && (rc = fill_zero_launch(g2, in_elems, s))) return hipfail(rc, "correlation_bwd");
-  CorrBwdGenericParams p{gout, d1, d2, g1, g2, N, C, H, W, md, kernel, s1, s2, pad, is_multiply ? 1 : 0, tc, th, tw, r, D, req1, req2};
-  const size_t total = (size_t)N * tc * th * tw;
-  return hipfail(launch("corr_bwd_scatter", corr_bwd_scatter_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, p),
-                 "correlation_bwd(generic)");
+  return hipfail(rc, "correlation_bwd");
 }
 
 int MFN_API(warp_bwd)(const float *gout, const float *x, const float *flow, float *gx, float *gflow, int N, int C, int H,
@@ -901,231 +926,248 @@ int MFN_API(grid_generator_warp_bwd)(const float *ggrid, float *gflow_xy, int N,
                         (hipStream_t)stream, p), "grid_generator_warp_bwd");
 }
 
-// the shared-offset kernel's conditions that the host can see (the offsets themselves are judged per strip on the device)
-static bool dc_bwd_shared_shape(int H, int W, int kh, int kw, int sh, int sw, int dh, int dw, int groups, int dg) {
-  return kh == 3 && kw == 3 && sh == 1 && sw == 1 && dh == 1 && dw == 1 && groups == 1 && dg == 1 && H < 65536 && W < 65536;
+// What dc_bwd_plan decides for a backward call of the deformable convolution and dc_bwd_exec launches, top to bottom.
+enum class DcBwdIn { None, Pix, Tile, Generic };
+enum class DcBwdW { None, PcSlabs, Pc, Mfma, Generic };
+struct DcBwdPlan {
+  DcBwdIn in;                  // input / offset gradient: dc_bwd_input_pix_kernel | dc_bwd_input_tile_kernel | dc_bwd_input_kernel
+  int tiles_x, tiles_y;        // Pix / Tile: DCI_TW x DCI_TH pixel tiles of an image
+  int pblocks, ksplit, xcd;    // Pix: channel blocks, filter slices over blockIdx.z, block order by XCD
+  int cchunk;                  // Generic: input channels per thread
+  DcBwdW w;                    // weight gradient: dc_bwd_weight_pc_kernel, its blocks' partial sums in workspace slabs (+ reduce launch) or
+                               // added to gw through atomics | dc_bwd_weight_mfma_kernel | dc_bwd_weight_kernel
+  int tx, ty, ntiles, cblocks, mtot, tpb, nblk;   // Pc*: 8x4-pixel tiles, channel blocks, filter tiles, tiles per block, blocks per channel block
+  int mto, slices;             // Mfma: filter tiles per block, pixel slices
+  bool bias_launch;            // dc_bwd_bias_kernel; otherwise the weight launch sums the bias as well (or none is requested)
+  bool zero[4];                // write-mode gx, goffset, gw, gbias that accumulate through atomics start from zero: cleared by fill_zero4, or ...
+  bool pc_zeroes;              // ... (gx, goffset) by the PcSlabs blocks on their way in: that launch then runs first, no fill launch
+  bool flow_ok;                // flow mode wanted and every kernel of the call reads the flow field in place of an offset tensor
+  size_t slab_bytes, ws_bytes; // the Pc slabs (weights' + bias'); what a size query answers
+};
+// p: shape and requests (Ho / Wo filled in).  What only a run knows: flow mode wanted (mfn_deform_conv_shared_bwd), 16-byte alignment of
+// x and w, usable bytes of a 16-byte aligned workspace; a size query plans an aligned call that brings all the workspace the plan wants.
+static DcBwdPlan dc_bwd_plan(const Settings &st, const DcBwdParams &p, bool flow = false, bool x16 = true, bool w16 = true,
+                             size_t ws_bytes = (size_t)-1) {
+  DcBwdPlan pl{};
+  const int N = p.N, Cin = p.Cin, H = p.H, W = p.W, Cout = p.Cout, T = p.kh * p.kw;
+  const bool fast = p.groups == 1 && p.dg == 1 && (st.t.path_generic & 2) == 0;
+  const bool same = p.sh == 1 && p.sw == 1 && p.Ho == H && p.Wo == W && H < 65536 && W < 65536;
+  // the shared-offset kernels' conditions that the host can see (the offsets themselves are judged per strip on the device)
+  const bool shared = p.kh == 3 && p.kw == 3 && p.dh == 1 && p.dw == 1 && p.groups == 1 && p.dg == 1 && same;
+  const bool fits30 = (size_t)N * Cin * H * W < ((size_t)1 << 30);
+  // ---- weight gradient.  Pc: in the forward's orientation (kernels/dc_backward.h), columns produced as the forward kernel does, pixels
+  // as the reduction dimension.  Up to three filter tiles: with four (level 5: one 4x8 tile per block) the per-block slab and the
+  // reduce launch cost more than the per-tap kernel's atomics (37 against 25 us)
+  const bool pc_shape = shared && W % 4 == 0 && Cout <= 96 && fits30;
+  pl.tx = cdiv(W, 8); pl.ty = cdiv(H, 4); pl.ntiles = N * pl.tx * pl.ty; pl.cblocks = cdiv(Cin, 32); pl.mtot = cdiv(Cout, 32);
+  pl.tpb = cdiv(pl.ntiles * pl.cblocks, 256);
+  if (pl.tpb < 1) pl.tpb = 1;
+  pl.nblk = cdiv(pl.ntiles, pl.tpb);
+  pl.slab_bytes = ((size_t)pl.cblocks * pl.nblk * pl.mtot * 32 * 288 + (size_t)pl.nblk * pl.mtot * 32) * sizeof(float);
+  pl.ws_bytes = pc_shape ? pl.slab_bytes : 0;   // whatever the requests and path.generic (kept from round 2)
+  const bool w_fast = p.req_w && fast && T <= 25;
+  if (w_fast && pc_shape && x16) pl.w = ws_bytes >= pl.slab_bytes ? DcBwdW::PcSlabs : DcBwdW::Pc;
+  else if (w_fast) {
+    // fp32-MFMA weight gradient: pixels are the reduction dimension, partial sums meet in gw through atomics.
+    // blocks = slices * jgroups * ogroups; every block ends with 32 x 32 atomics per wave into the same gw, so the
+    // block count trades parallelism against atomic traffic
+    // measured (tools/bwd_levels.py, cfg2): 512 blocks -- 27 / 62 / 84 / 142 us at levels 5..2 against 42 / 65 / 113 / 178 with 1024
+    pl.w = DcBwdW::Mfma;
+    pl.mto = Cout > 32 ? 2 : 1;
+    const int tiles = cdiv((int)((size_t)N * p.Ho * p.Wo), 32), jgroups = cdiv(cdiv(Cin * T, 32), 4), ogroups = cdiv(Cout, pl.mto * 32);
+    pl.slices = 512 / (jgroups * ogroups);
+    pl.slices = pl.slices < 1 ? 1 : (pl.slices > tiles ? tiles : pl.slices);
+  } else if (p.req_w) pl.w = DcBwdW::Generic;
+  pl.bias_launch = p.req_bias && (pl.w == DcBwdW::None || pl.w == DcBwdW::Generic);
+  const bool w_atomics = pl.w == DcBwdW::Pc || pl.w == DcBwdW::Mfma;
+  pl.zero[0] = p.req_x == MFN_REQ_WRITE;
+  pl.zero[1] = p.req_offset == MFN_REQ_WRITE;
+  pl.zero[2] = w_atomics && p.req_w == MFN_REQ_WRITE;
+  pl.zero[3] = w_atomics && p.req_bias == MFN_REQ_WRITE;
+  pl.pc_zeroes = pl.w == DcBwdW::PcSlabs && (pl.zero[0] || pl.zero[1]);
+  // ---- input / offset gradient.  Tile: fp32-MFMA column gradient + LDS-privatised scatter (kernels/backward.h), every tap of every
+  // strip.  Pix: lane = pixel (kernels/dc_backward.h), 8x16-pixel regions x 16 channels, two blocks per CU, all nine taps in one pass
+  // where they share one offset per pixel (the reference's only use); tiles that do not qualify are done tap by tap by the same blocks
+  const bool tile_ok = fast && same && T <= 9;
+  const bool pix_ok = tile_ok && shared && (st.t.bwd_off & 1) == 0 && W % 4 == 0 && Cin % 4 == 0 && x16 && w16 && fits30 &&
+                      (size_t)Cout * H * W < ((size_t)1 << 29) && (size_t)Cout * Cin * 9 < ((size_t)1 << 29);
+  pl.tiles_x = cdiv(W, DCI_TW); pl.tiles_y = cdiv(H, DCI_TH);
+  if (!p.req_x && !p.req_offset) pl.in = DcBwdIn::None;
+  else if (pix_ok) {
+    pl.in = DcBwdIn::Pix;
+    const int tiles8 = N * pl.tiles_x * pl.tiles_y;
+    pl.pblocks = cdiv(Cin, DCP_CB);
+    pl.xcd = (pl.pblocks == 1 || tiles8 % 8 == 0) ? 1 : 0;
+    // fewer blocks than the chip has CUs (coarse levels): the filters are split over blockIdx.z (chunks of 16) up to ONE
+    // block per CU -- every slice repeats everything behind the K loop, and two such blocks on a CU slow each other
+    // (level 5, same box: 256 slots 35.4-36.9 us, 512 slots 37.9-38.2, 128 slots 40.3)
+    pl.ksplit = 256 / (tiles8 * pl.pblocks);
+    pl.ksplit = pl.ksplit < 1 ? 1 : (pl.ksplit > cdiv(Cout, DCP_KO) ? cdiv(Cout, DCP_KO) : pl.ksplit);
+  } else if (tile_ok) pl.in = DcBwdIn::Tile;
+  else {
+    pl.in = DcBwdIn::Generic;   // enough threads to fill the chip: the input channels of a pixel over several threads when pixels are few
+    const long px = (long)N * p.Ho * p.Wo;
+    long want = (65536 + px - 1) / px;
+    want = want < 1 ? 1 : (want > Cin ? Cin : want);
+    pl.cchunk = (int)((Cin + want - 1) / want);
+  }
+  pl.flow_ok = flow && (st.t.bwd_off & 2) == 0 && pix_ok && (!p.req_w || pc_shape);
+  return pl;
 }
-// the lane = pixel weight gradient (kernels/dc_backward.h): tiles per block, blocks per channel block, slab bytes
-struct DcBwdWPlan { int ok, tx, ty, ntiles, cblocks, mtot, tpb, nblk; size_t slab_bytes; };
-static DcBwdWPlan dc_bwd_wplan(int N, int Cin, int H, int W, int Cout) {
-  DcBwdWPlan q{};
-  // up to three filter tiles: with four (level 5: one 4x8 tile per block) the per-block slab and the reduce launch cost more
-  // than the per-tap kernel's atomics (37 against 25 us)
-  q.ok = W % 4 == 0 && Cout <= 96 && (size_t)N * Cin * H * W < ((size_t)1 << 30);
-  q.tx = cdiv(W, 8); q.ty = cdiv(H, 4); q.ntiles = N * q.tx * q.ty; q.cblocks = cdiv(Cin, 32); q.mtot = cdiv(Cout, 32);
-  q.tpb = cdiv(q.ntiles * q.cblocks, 256);
-  if (q.tpb < 1) q.tpb = 1;
-  q.nblk = cdiv(q.ntiles, q.tpb);
-  q.slab_bytes = ((size_t)q.cblocks * q.nblk * q.mtot * 32 * 288 + (size_t)q.nblk * q.mtot * 32) * sizeof(float);  // weights' + bias'
-  return q;
+static size_t dc_bwd_ws_bytes(const Settings &st, int N, int Cin, int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph, int pw,
+                              int dh, int dw, int groups, int dg) {
+  DcBwdParams p{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, N, Cin, H, W, Cout, 0, 0, kh, kw, sh, sw, ph, pw,
+                dh, dw, groups, dg, 0, 0, 0, 0, 1};
+  if (N <= 0 || Cin <= 0 || Cout <= 0 || MFN_API(deform_conv_out_shape)(H, W, kh, kw, sh, sw, ph, pw, dh, dw, &p.Ho, &p.Wo)) return 0;
+  return dc_bwd_plan(st, p).ws_bytes;
 }
-// workspace of the backward: the weight gradient's per-block slabs (round 2 also kept a flag per 4x8-pixel tile here)
+// workspace of the backward: the weight gradient's per-block slabs (the column gradient is formed on the fly)
 size_t MFN_API(deform_conv_bwd_workspace_bytes)(int N, int Cin, int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph, int pw,
                                                 int dh, int dw, int groups, int dg) {
-  // the column gradient is formed on the fly; scratch: the weight gradient's per-block slabs
-  if (N <= 0 || Cin <= 0 || H <= 0 || W <= 0 || !dc_bwd_shared_shape(H, W, kh, kw, sh, sw, dh, dw, groups, dg)) return 0;
-  if (H + 2 * ph - 2 != H || W + 2 * pw - 2 != W) return 0;  // Ho == H, Wo == W
-  const DcBwdWPlan q = dc_bwd_wplan(N, Cin, H, W, Cout > 0 ? Cout : 1);
-  return (q.ok && Cout > 0) ? q.slab_bytes : 0;
+  return dc_bwd_ws_bytes(settings_now(), N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, dg);
 }
 
 // flow mode of the backward (mfn_deform_conv_shared_bwd): the kernels of kernels/dc_backward.h read the flow field in place of an
-// offset tensor and write d/dflow in place of goffset.  Only where dc_bwd_flow_direct(st, ) says those kernels take the whole call.
-struct DcFlowArgs { const float *flow; float *gflow; float scale, stride; };
-static bool dc_bwd_flow_direct(const Settings &st, const float *x, const float *w, int N, int Cin, int H, int W, int Cout, int kh, int kw, int ph, int pw,
-                               int dh, int dw, int groups, int req_w, const void *workspace, size_t ws_bytes) {
-  if ((st.t.bwd_off & 2) != 0 || (st.t.path_generic & 2) != 0 || (st.t.bwd_off & 1) != 0)
-    return false;
-  if (N <= 0 || !dc_bwd_shared_shape(H, W, kh, kw, 1, 1, dh, dw, groups, 1) || ph != 1 || pw != 1) return false;
-  if (W % 4 != 0 || Cin % 4 != 0 || !aligned(x, 16) || !aligned(w, 16) || !aligned(workspace, 16)) return false;
-  if ((size_t)N * Cin * H * W >= ((size_t)1 << 30) || (size_t)Cout * H * W >= ((size_t)1 << 29) || (size_t)Cout * Cin * 9 >= ((size_t)1 << 29))
-    return false;
-  (void)ws_bytes;
-  return !req_w || dc_bwd_wplan(N, Cin, H, W, Cout).ok;
+// offset tensor and write d/dflow in place of goffset (p.goffset).  Only where the plan says they take the whole call (flow_ok).
+struct DcFlowArgs { const float *flow; float scale, stride; };
+static int dc_bwd_weight_pc(const DcBwdPlan &pl, const DcBwdParams &p, float *slabs, const DcFlowArgs *fl, float *const zero[2],
+                            const size_t zero_n[2], hipStream_t s) {
+  DcBwdWPParams wp{p.gout, p.x, p.offset, p.gw, p.req_bias ? p.gbias : nullptr, p.N, p.Cin, p.H, p.W, p.Cout, p.ph, p.pw, pl.tx, pl.ty, pl.ntiles,
+                   1.f / (float)(pl.tx * pl.ty), 1.f / (float)pl.tx, pl.tpb, slabs,
+                   slabs ? slabs + (size_t)pl.cblocks * pl.nblk * pl.mtot * 32 * 288 : nullptr,
+                   (p.req_x || p.req_offset) ? nullptr : (unsigned long long *)((unsigned long long)g_timeline & ~1ull),
+                   fl ? fl->flow : nullptr, fl ? fl->scale : 0.f, fl ? fl->stride : 1.f,
+                   {zero ? zero[0] : nullptr, zero ? zero[1] : nullptr}, {zero ? zero_n[0] : 0, zero ? zero_n[1] : 0}};
+  const dim3 grid(pl.nblk, pl.cblocks);
+  const size_t lds2 = dc_bwd_weight_pc_lds_bytes(pl.mtot);   // producer / consumer waves (eight per block)
+  int rc = pl.mtot == 1 ? launch("dc_bwd_weight_pc", dc_bwd_weight_pc_kernel<1>, grid, dim3(512), lds2, s, wp)
+         : pl.mtot == 2 ? launch("dc_bwd_weight_pc", dc_bwd_weight_pc_kernel<2>, grid, dim3(512), lds2, s, wp)
+                        : launch("dc_bwd_weight_pc", dc_bwd_weight_pc_kernel<3>, grid, dim3(512), lds2, s, wp);
+  if (rc || !slabs) return rc;
+  // the blocks' partial sums are added in block order
+  const int wblocks = (int)(((size_t)p.Cout * p.Cin * 9 + 15) / 16), bblocks = p.req_bias ? cdiv(p.Cout, 16) : 0;
+  DcBwdWRParams rp{slabs, wp.bias_slabs, p.gw, p.gbias, p.Cin, p.Cout, pl.mtot, pl.nblk, p.req_w == MFN_REQ_ADD ? 1 : 0,
+                   p.req_bias == MFN_REQ_ADD ? 1 : 0, wblocks};
+  return launch("dc_bwd_weight_reduce", dc_bwd_weight_reduce_kernel, dim3((unsigned)(wblocks + bblocks)), dim3(256), 256 * sizeof(float), s, rp);
 }
-static int dc_bwd_run(const Settings &st, const float *gout, const float *x, const float *offset, const float *w, float *gx,
-                      float *goffset, float *gw, float *gbias, int N, int Cin, int H, int W, int Cout, int kh,
-                      int kw, int sh, int sw, int ph, int pw, int dh, int dw, int groups, int dg, int req_x,
-                      int req_offset, int req_w, int req_bias, void *workspace, size_t ws_bytes, void *stream, const DcFlowArgs *fl) {
-  int Ho, Wo;
-  int rc = dc_check("deform_conv_bwd", x, w, gout, N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, dg, &Ho, &Wo);
+// the launches of a plan, in order; returns a HIP status.  fl: flow mode (pl.flow_ok)
+static int dc_bwd_exec(const DcBwdPlan &pl, DcBwdParams p, void *workspace, const DcFlowArgs *fl, hipStream_t s) {
+  const size_t oplane = (size_t)p.Ho * p.Wo;
+  const int T = p.kh * p.kw;
+  float *const slabs = pl.w == DcBwdW::PcSlabs ? (float *)workspace : nullptr;
+  float *const zp[4] = {pl.zero[0] ? p.gx : nullptr, pl.zero[1] ? p.goffset : nullptr, pl.zero[2] ? p.gw : nullptr, pl.zero[3] ? p.gbias : nullptr};
+  const size_t zn[4] = {(size_t)p.N * p.Cin * p.H * p.W, fl ? (size_t)p.N * 2 * oplane : (size_t)p.N * 2 * T * p.dg * oplane,
+                        (size_t)p.Cout * p.Cin * T, (size_t)p.Cout};
+  int rc = pl.pc_zeroes ? dc_bwd_weight_pc(pl, p, slabs, fl, zp, zn, s) : fill_zero4_launch(zp, zn, s);   // one launch for all of them
   if (rc) return rc;
-  if (fl) { offset = nullptr; goffset = fl->gflow; }
-  if (N != 0 && !offset && !fl) return fail(MFN_E_NULL, "deform_conv_bwd: NULL offset");
-  if (!req_ok(req_x) || !req_ok(req_offset) || !req_ok(req_w) || !req_ok(req_bias))
-    return fail(MFN_E_PARAM, "deform_conv_bwd: req must be 0 (null), 1 (write) or 3 (add)");
-  if ((N != 0 && ((req_x && !gx) || (req_offset && !goffset))) || (req_w && !gw) || (req_bias && !gbias))
-    return fail(MFN_E_NULL, "deform_conv_bwd: NULL gradient output");
-  hipStream_t s = (hipStream_t)stream;
-  if (N == 0) {  // empty batch: the parameter gradients are zero
-    if (req_w == MFN_REQ_WRITE && (rc = fill_zero_launch(gw, (size_t)Cout * (Cin / groups) * kh * kw, s))) return hipfail(rc, "deform_conv_bwd");
-    if (req_bias == MFN_REQ_WRITE && (rc = fill_zero_launch(gbias, (size_t)Cout, s))) return hipfail(rc, "deform_conv_bwd");
-    return 0;
-  }
-  const size_t oplane = (size_t)Ho * Wo;
-  DcBwdParams p{gout, x, offset, w, gx, goffset, gw, gbias, N, Cin, H, W, Cout, Ho, Wo, kh, kw, sh, sw, ph, pw, dh, dw,
-                groups, dg, req_x, req_offset, req_w, req_bias, 1};
-  const bool w_mfma = req_w && groups == 1 && dg == 1 && (st.t.path_generic & 2) == 0 && kh * kw <= 25;
-  // The weight / bias gradient in the forward's orientation (kernels/dc_backward.h: dc_bwd_weight_pc_kernel): columns produced
-  // as the forward kernel does, pixels as the reduction dimension; the blocks' partial sums go through the workspace (when it
-  // has the room) and are added in block order.  `zero`: write-mode gradients of the OTHER kernels of this call (gx, goffset)
-  // that the blocks clear on their way in -- the launch then runs first and the separate fill launch is not needed.
-  const DcBwdWPlan wq = dc_bwd_wplan(N, Cin, H, W, Cout);
-  const bool w_pc = w_mfma && wq.ok && dc_bwd_shared_shape(H, W, kh, kw, sh, sw, dh, dw, groups, dg) && Ho == H && Wo == W && aligned(x, 16);
-  float *const slabs = (w_pc && workspace && ws_bytes >= wq.slab_bytes && aligned(workspace, 16)) ? (float *)workspace : nullptr;
-  auto weight_pc = [&](float *const zero[2], const size_t zero_n[2]) -> int {
-    DcBwdWPParams wp{gout, x, offset, gw, req_bias ? gbias : nullptr, N, Cin, H, W, Cout, ph, pw, wq.tx, wq.ty, wq.ntiles,
-                     1.f / (float)(wq.tx * wq.ty), 1.f / (float)wq.tx, wq.tpb, slabs,
-                     slabs ? slabs + (size_t)wq.cblocks * wq.nblk * wq.mtot * 32 * 288 : nullptr,
-                     (req_x || req_offset) ? nullptr : (unsigned long long *)((unsigned long long)g_timeline & ~1ull),
-                     fl ? fl->flow : nullptr, fl ? fl->scale : 0.f, fl ? fl->stride : 1.f,
-                     {zero ? zero[0] : nullptr, zero ? zero[1] : nullptr}, {zero ? zero_n[0] : 0, zero ? zero_n[1] : 0}};
-    const int bias_req = req_bias;
-    req_bias = 0;  // done by the same launch
-    const dim3 grid(wq.nblk, wq.cblocks);
-    const int mtot = wq.mtot;
-    const size_t lds2 = dc_bwd_weight_pc_lds_bytes(mtot);   // producer / consumer waves (eight per block)
-    int r = mtot == 1 ? launch("dc_bwd_weight_pc", dc_bwd_weight_pc_kernel<1>, grid, dim3(512), lds2, s, wp)
-          : mtot == 2 ? launch("dc_bwd_weight_pc", dc_bwd_weight_pc_kernel<2>, grid, dim3(512), lds2, s, wp)
-                      : launch("dc_bwd_weight_pc", dc_bwd_weight_pc_kernel<3>, grid, dim3(512), lds2, s, wp);
-    if (r) return r;
-    if (slabs) {
-      const size_t total = (size_t)Cout * Cin * 9;
-      const int wblocks = (int)((total + 15) / 16), bblocks = bias_req ? cdiv(Cout, 16) : 0;
-      DcBwdWRParams rp{slabs, wp.bias_slabs, gw, gbias, Cin, Cout, mtot, wq.nblk, req_w == MFN_REQ_ADD ? 1 : 0,
-                       bias_req == MFN_REQ_ADD ? 1 : 0, wblocks};
-      r = launch("dc_bwd_weight_reduce", dc_bwd_weight_reduce_kernel, dim3((unsigned)(wblocks + bblocks)), dim3(256), 256 * sizeof(float), s, rp);
+  unsigned long long *const timeline = (unsigned long long *)((unsigned long long)g_timeline & ~1ull);
+  switch (pl.in) {
+    case DcBwdIn::None: break;
+    case DcBwdIn::Pix: {
+      DcBwdPParams pp{p.gout, p.x, p.offset, p.w, p.gx, p.goffset, p.N, p.Cin, p.H, p.W, p.Cout, p.ph, p.pw, pl.tiles_x, pl.tiles_y,
+                      1.f / (float)(pl.tiles_x * pl.tiles_y), 1.f / (float)pl.tiles_x, p.req_x, p.req_offset, pl.xcd, timeline,
+                      (int)((unsigned long long)g_timeline & 1ull), fl ? fl->flow : nullptr, fl ? p.goffset : nullptr, fl ? fl->scale : 0.f,
+                      fl ? fl->stride : 1.f};
+      rc = launch("dc_bwd_input_pix", dc_bwd_input_pix_kernel, dim3(p.N * pl.tiles_x * pl.tiles_y, pl.pblocks, pl.ksplit), dim3(256),
+                  dc_bwd_input_pix_lds_bytes(), s, pp);
+      break;
     }
-    return r;
-  };
-  bool weights_done = false;
-  {  // every gradient that accumulates through atomics starts from zero in write mode
-    float *zp[4] = {req_x == MFN_REQ_WRITE ? gx : nullptr, req_offset == MFN_REQ_WRITE ? goffset : nullptr,
-                    (w_mfma && !slabs && req_w == MFN_REQ_WRITE) ? gw : nullptr, (w_mfma && !slabs && req_bias == MFN_REQ_WRITE) ? gbias : nullptr};
-    const size_t zn[4] = {(size_t)N * Cin * H * W, fl ? (size_t)N * 2 * oplane : (size_t)N * 2 * kh * kw * dg * oplane,
-                          (size_t)Cout * Cin * kh * kw, (size_t)Cout};
-    if (slabs && (zp[0] || zp[1])) {   // the slab form writes gw / gbias itself: its blocks clear gx / goffset, no fill launch
-      if ((rc = weight_pc(zp, zn))) return hipfail(rc, "deform_conv_bwd");
-      weights_done = true;
-    } else if ((rc = fill_zero4_launch(zp, zn, s))) {   // one launch for all of them
-      return hipfail(rc, "deform_conv_bwd");
-    }
-  }
-  if (req_x || req_offset) {
-    if (groups == 1 && dg == 1 && sh == 1 && sw == 1 && Ho == H && Wo == W && H < 65536 && W < 65536 && kh * kw <= 9 &&
-        (st.t.path_generic & 2) == 0) {
-      // fp32-MFMA column gradient + LDS-privatised scatter (kernels/backward.h: dc_bwd_input_tile_kernel)
-      DcBwdIParams ip{gout, x, offset, w, gx, goffset, N, Cin, H, W, Cout, kh, kw, ph, pw, dh, dw, kh * kw,
-                      cdiv(W, DCI_TW), cdiv(H, DCI_TH), req_x, req_offset,
-                      (unsigned long long *)((unsigned long long)g_timeline & ~1ull)};
-      if (fl) { ip.flow = fl->flow; ip.gflow = fl->gflow; ip.flow_scale = fl->scale; ip.flow_stride = fl->stride; }
-      if ((st.t.bwd_off & 1) == 0 && dc_bwd_shared_shape(H, W, kh, kw, sh, sw, dh, dw, groups, dg) &&
-          (size_t)Cout * H * W < ((size_t)1 << 29) && (size_t)Cout * Cin * 9 < ((size_t)1 << 29)) {
-        // all nine taps in one pass where they share one offset per pixel (the reference's only use); tiles that do not
-        // qualify are done tap by tap by the same blocks
-        const int tiles8 = N * ip.tiles_x * ip.tiles_y;
-        if (W % 4 == 0 && Cin % 4 == 0 && aligned(x, 16) && aligned(w, 16) &&
-            (size_t)N * Cin * H * W < ((size_t)1 << 30)) {
-          // lane = pixel (kernels/dc_backward.h): 8x16-pixel regions x 16 channels, two blocks per CU
-          const int pblocks = cdiv(Cin, DCP_CB);
-          DcBwdPParams pp{gout, x, offset, w, gx, goffset, N, Cin, H, W, Cout, ph, pw, ip.tiles_x, ip.tiles_y,
-                          1.f / (float)(ip.tiles_x * ip.tiles_y), 1.f / (float)ip.tiles_x, req_x, req_offset,
-                          (pblocks == 1 || tiles8 % 8 == 0) ? 1 : 0, ip.timeline, (int)((unsigned long long)g_timeline & 1ull),
-                          fl ? fl->flow : nullptr, fl ? fl->gflow : nullptr, fl ? fl->scale : 0.f, fl ? fl->stride : 1.f};
-          // fewer blocks than the chip has CUs (coarse levels): the filters are split over blockIdx.z (chunks of 16) up to ONE
-          // block per CU -- every slice repeats everything behind the K loop, and two such blocks on a CU slow each other
-          // (level 5, same box: 256 slots 35.4-36.9 us, 512 slots 37.9-38.2, 128 slots 40.3)
-          int ksplit = 256 / (tiles8 * pblocks);
-          ksplit = ksplit < 1 ? 1 : (ksplit > cdiv(Cout, DCP_KO) ? cdiv(Cout, DCP_KO) : ksplit);
-          const dim3 pgrid(tiles8, pblocks, ksplit);
-          rc = launch("dc_bwd_input_pix", dc_bwd_input_pix_kernel, pgrid, dim3(256), dc_bwd_input_pix_lds_bytes(), s, pp);
-          if (rc) return hipfail(rc, "deform_conv_bwd");
-          goto input_done;
-        }
-        // shapes the lane = pixel kernel does not take (W % 4, Cin % 4, unaligned tensors): the tile kernel below does every
-        // tap of every strip (the round-1 lane = channel shared-offset kernel that stood here was removed in round 3)
-        if (fl) return fail(MFN_E_PARAM, "deform_conv_shared_bwd: internal: flow mode outside the lane = pixel kernels");
-      }
-      rc = launch("dc_bwd_input_tile", dc_bwd_input_tile_kernel, dim3(N * ip.tiles_x * ip.tiles_y, cdiv(Cin, 32)), dim3(256),
+    case DcBwdIn::Tile: {
+      DcBwdIParams ip{p.gout, p.x, p.offset, p.w, p.gx, p.goffset, p.N, p.Cin, p.H, p.W, p.Cout, p.kh, p.kw, p.ph, p.pw, p.dh, p.dw, T,
+                      pl.tiles_x, pl.tiles_y, p.req_x, p.req_offset, timeline};
+      rc = launch("dc_bwd_input_tile", dc_bwd_input_tile_kernel, dim3(p.N * pl.tiles_x * pl.tiles_y, cdiv(p.Cin, 32)), dim3(256),
                   dc_bwd_input_lds_bytes(), s, ip);
-      if (rc) return hipfail(rc, "deform_conv_bwd");
-      goto input_done;
+      break;
     }
-    // enough threads to fill the chip: split the input channels of a pixel over several threads when pixels are few
-    long want = (65536 + (long)(N * oplane) - 1) / (long)(N * oplane);
-    if (want < 1) want = 1;
-    if (want > Cin) want = Cin;
-    p.cchunk = (int)((Cin + want - 1) / want);
-    const size_t total = (size_t)N * oplane * ((Cin + p.cchunk - 1) / p.cchunk);
-    rc = launch("dc_bwd_input", dc_bwd_input_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, p);
-    if (rc) return hipfail(rc, "deform_conv_bwd");
+    case DcBwdIn::Generic: {
+      p.cchunk = pl.cchunk;
+      const size_t total = (size_t)p.N * oplane * ((p.Cin + p.cchunk - 1) / p.cchunk);
+      rc = launch("dc_bwd_input", dc_bwd_input_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, p);
+    }
   }
-input_done:
-  if (weights_done) {
-  } else if (w_pc) {
-    if ((rc = weight_pc(nullptr, nullptr))) return hipfail(rc, "deform_conv_bwd");
-  } else if (fl && req_w) {
-    return fail(MFN_E_PARAM, "deform_conv_shared_bwd: internal: flow mode outside the lane = pixel kernels");
-  } else if (w_mfma) {
-    // fp32-MFMA weight gradient: pixels are the reduction dimension, partial sums meet in gw (zeroed above) through atomics
-    DcBwdWParams wp{gout, x, offset, gw, req_bias ? gbias : nullptr, N, Cin, H, W, Cout, Ho, Wo, kh, kw, sh, sw, ph, pw, dh, dw,
-                    (int)((size_t)N * oplane), Cin * kh * kw, kh * kw, 1};
-    req_bias = 0;  // done by the same launch
-    const int tiles = cdiv(wp.P, 32), jgroups = cdiv(cdiv(wp.K2, 32), 4);
-    const int mto = Cout > 32 ? 2 : 1, ogroups = cdiv(Cout, mto * 32);
-    // blocks = slices * jgroups * ogroups; every block ends with 32 x 32 atomics per wave into the same gw, so the
-    // block count trades parallelism against atomic traffic (tuning key dc.bwdwblocks, 0 = default)
-    // measured (tools/bwd_levels.py, cfg2): 512 blocks -- 27 / 62 / 84 / 142 us at levels 5..2 against 42 / 65 / 113 / 178 with 1024
-    int slices = 512 / (jgroups * ogroups);
-    if (slices < 1) slices = 1;
-    if (slices > tiles) slices = tiles;
-    rc = mto == 2 ? dc_bwd_weight_mfma_launch<2>(wp, slices, s) : dc_bwd_weight_mfma_launch<1>(wp, slices, s);
-    if (rc) return hipfail(rc, "deform_conv_bwd");
-  } else if (req_w) {
-    const int opg = Cout / groups;
-    const int blocks = Cin * kh * kw * ((opg + DC_BW_OC - 1) / DC_BW_OC);
-    rc = launch("dc_bwd_weight", dc_bwd_weight_kernel, dim3(blocks), dim3(256), (size_t)DC_BW_OC * 256 * sizeof(float), s, p);
-    if (rc) return hipfail(rc, "deform_conv_bwd");
+  if (rc) return rc;
+  switch (pl.w) {
+    case DcBwdW::None: break;
+    case DcBwdW::PcSlabs:
+    case DcBwdW::Pc:
+      if (!pl.pc_zeroes) rc = dc_bwd_weight_pc(pl, p, slabs, fl, nullptr, nullptr, s);
+      break;
+    case DcBwdW::Mfma: {
+      DcBwdWParams wp{p.gout, p.x, p.offset, p.gw, p.req_bias ? p.gbias : nullptr, p.N, p.Cin, p.H, p.W, p.Cout, p.Ho, p.Wo, p.kh, p.kw, p.sh, p.sw,
+                      p.ph, p.pw, p.dh, p.dw, (int)((size_t)p.N * oplane), p.Cin * T, T, 1};
+      rc = pl.mto == 2 ? dc_bwd_weight_mfma_launch<2>(wp, pl.slices, s) : dc_bwd_weight_mfma_launch<1>(wp, pl.slices, s);
+      break;
+    }
+    case DcBwdW::Generic:
+      rc = launch("dc_bwd_weight", dc_bwd_weight_kernel, dim3(p.Cin * T * cdiv(p.Cout / p.groups, DC_BW_OC)), dim3(256),
+                  (size_t)DC_BW_OC * 256 * sizeof(float), s, p);
   }
-  if (req_bias) {
-    rc = launch("dc_bwd_bias", dc_bwd_bias_kernel, dim3(Cout), dim3(256), 256 * sizeof(float), s, p);
-    if (rc) return hipfail(rc, "deform_conv_bwd");
-  }
+  if (!rc && pl.bias_launch) rc = launch("dc_bwd_bias", dc_bwd_bias_kernel, dim3(p.Cout), dim3(256), 256 * sizeof(float), s, p);
+  return rc;
+}
+
+// the checks every backward call of the deformable convolution makes (p.Ho / p.Wo filled in), then its requests and gradient pointers
+static int dc_bwd_dims(const char *what, DcBwdParams &p) {
+  return dc_check(what, p.x, p.w, p.gout, p.N, p.Cin, p.H, p.W, p.Cout, p.kh, p.kw, p.sh, p.sw, p.ph, p.pw, p.dh, p.dw, p.groups, p.dg, &p.Ho, &p.Wo);
+}
+static int dc_bwd_reqs(const DcBwdParams &p) {
+  if (!req_ok(p.req_x) || !req_ok(p.req_offset) || !req_ok(p.req_w) || !req_ok(p.req_bias))
+    return fail(MFN_E_PARAM, "deform_conv_bwd: req must be 0 (null), 1 (write) or 3 (add)");
+  if ((p.N != 0 && ((p.req_x && !p.gx) || (p.req_offset && !p.goffset))) || (p.req_w && !p.gw) || (p.req_bias && !p.gbias))
+    return fail(MFN_E_NULL, "deform_conv_bwd: NULL gradient output");
   return 0;
+}
+static int dc_bwd_empty(const DcBwdParams &p, hipStream_t s) {   // empty batch: the parameter gradients are zero
+  int rc = p.req_w == MFN_REQ_WRITE ? fill_zero_launch(p.gw, (size_t)p.Cout * (p.Cin / p.groups) * p.kh * p.kw, s) : 0;
+  if (!rc && p.req_bias == MFN_REQ_WRITE) rc = fill_zero_launch(p.gbias, (size_t)p.Cout, s);
+  return hipfail(rc, "deform_conv_bwd");
+}
+static int dc_bwd_run(const Settings &st, DcBwdParams p, void *workspace, size_t ws_bytes, hipStream_t s) {
+  int rc = dc_bwd_dims("deform_conv_bwd", p);
+  if (rc) return rc;
+  if (p.N != 0 && !p.offset) return fail(MFN_E_NULL, "deform_conv_bwd: NULL offset");
+  if ((rc = dc_bwd_reqs(p))) return rc;
+  if (p.N == 0) return dc_bwd_empty(p, s);
+  const DcBwdPlan pl = dc_bwd_plan(st, p, false, aligned(p.x, 16), aligned(p.w, 16), workspace && aligned(workspace, 16) ? ws_bytes : 0);
+  return hipfail(dc_bwd_exec(pl, p, workspace, nullptr, s), "deform_conv_bwd");
 }
 
 int MFN_API(deform_conv_bwd)(const float *gout, const float *x, const float *offset, const float *w, float *gx,
                              float *goffset, float *gw, float *gbias, int N, int Cin, int H, int W, int Cout, int kh,
                              int kw, int sh, int sw, int ph, int pw, int dh, int dw, int groups, int dg, int req_x,
                              int req_offset, int req_w, int req_bias, void *workspace, size_t ws_bytes, void *stream) {
-  return dc_bwd_run(settings_now(), gout, x, offset, w, gx, goffset, gw, gbias, N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, dg, req_x,
-                    req_offset, req_w, req_bias, workspace, ws_bytes, stream, nullptr);
+  const DcBwdParams p{gout, x, offset, w, gx, goffset, gw, gbias, N, Cin, H, W, Cout, 0, 0, kh, kw, sh, sw, ph, pw, dh, dw,
+                      groups, dg, req_x, req_offset, req_w, req_bias, 1};
+  return dc_bwd_run(settings_now(), p, workspace, ws_bytes, (hipStream_t)stream);
 }
 
 // gradient of mfn_offsets_from_flow
+static int offsets_from_flow_bwd_run(const float *goffset, float *gflow, int N, int H, int W, int taps, float scale, float stride, int req,
+                                     hipStream_t s) {
+  const size_t total = (size_t)N * 2 * H * W;
+  if (!total) return 0;
+  OffsetsBwdParams p{goffset, gflow, N, H, W, taps, scale, stride, req};
+  return hipfail(launch("offsets_from_flow_bwd", offsets_from_flow_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, p),
+                 "offsets_from_flow_bwd");
+}
 int MFN_API(offsets_from_flow_bwd)(const float *goffset, float *gflow, int N, int H, int W, int taps, float scale, float stride,
                                    int req, void *stream) {
   if (N != 0 && (!goffset || !gflow)) return fail(MFN_E_NULL, "offsets_from_flow_bwd: NULL tensor pointer");
   if (N < 0 || H <= 0 || W <= 0 || taps < 1) return fail(MFN_E_SHAPE, "offsets_from_flow_bwd: bad shape");
   if (stride == 0.f) return fail(MFN_E_PARAM, "offsets_from_flow_bwd: stride must be non-zero");
   if (req != MFN_REQ_WRITE && req != MFN_REQ_ADD) return fail(MFN_E_PARAM, "offsets_from_flow_bwd: req must be 1 (write) or 3 (add)");
-  const size_t total = (size_t)N * 2 * H * W;
-  if (!total) return 0;
-  OffsetsBwdParams p{goffset, gflow, N, H, W, taps, scale, stride, req};
-  return hipfail(launch("offsets_from_flow_bwd", offsets_from_flow_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
-                        (hipStream_t)stream, p), "offsets_from_flow_bwd");
+  return offsets_from_flow_bwd_run(goffset, gflow, N, H, W, taps, scale, stride, req, (hipStream_t)stream);
 }
 
-// Backward of the fused call (mfn_deform_conv_shared_fwd): the offsets and their gradient live in the workspace,
-// [offset N x 2T x H x W][goffset, the same][workspace of mfn_deform_conv_bwd]
+// Backward of the fused call (mfn_deform_conv_shared_fwd): where the plan has no flow mode the offsets and their gradient live in the
+// workspace, [offset N x 2T x H x W][goffset, the same][workspace of mfn_deform_conv_bwd]
 static size_t dc_shared_bwd_off_bytes(int N, int H, int W, int kh, int kw) {
   return ((size_t)N * 2 * kh * kw * H * W * sizeof(float) + 255) / 256 * 256;
 }
 size_t MFN_API(deform_conv_shared_bwd_workspace_bytes)(int N, int Cin, int H, int W, int Cout, int kh, int kw, int ph, int pw,
                                                        int dh, int dw, int groups) {
   if (N <= 0 || Cin <= 0 || H <= 0 || W <= 0 || kh <= 0 || kw <= 0) return 0;
-  return 2 * dc_shared_bwd_off_bytes(N, H, W, kh, kw) +
-         MFN_API(deform_conv_bwd_workspace_bytes)(N, Cin, H, W, Cout, kh, kw, 1, 1, ph, pw, dh, dw, groups, 1);
+  return 2 * dc_shared_bwd_off_bytes(N, H, W, kh, kw) + dc_bwd_ws_bytes(settings_now(), N, Cin, H, W, Cout, kh, kw, 1, 1, ph, pw, dh, dw, groups, 1);
 }
 int MFN_API(deform_conv_shared_bwd)(const float *gout, const float *x, const float *flow, float flow_scale, float flow_stride,
                                     const float *w, float *gx, float *gflow, float *gw, float *gbias, int N, int Cin, int H,
@@ -1136,26 +1178,31 @@ int MFN_API(deform_conv_shared_bwd)(const float *gout, const float *x, const flo
   if (flow_stride == 0.f) return fail(MFN_E_PARAM, "deform_conv_shared_bwd: flow_stride must be non-zero");
   if (!req_ok(req_flow)) return fail(MFN_E_PARAM, "deform_conv_shared_bwd: req must be 0 (null), 1 (write) or 3 (add)");
   if (N != 0 && req_flow && !gflow) return fail(MFN_E_NULL, "deform_conv_shared_bwd: NULL gradient output");
-  int Ho, Wo;
-  int rc = dc_check("deform_conv_shared_bwd", x, w, gout, N, Cin, H, W, Cout, kh, kw, 1, 1, ph, pw, dh, dw, groups, 1, &Ho, &Wo);
+  DcBwdParams p{gout, x, nullptr, w, gx, gflow, gw, gbias, N, Cin, H, W, Cout, 0, 0, kh, kw, 1, 1, ph, pw, dh, dw, groups, 1,
+                req_x, req_flow, req_w, req_bias, 1};
+  int rc = dc_bwd_dims("deform_conv_shared_bwd", p);
   if (rc) return rc;
-  if (Ho != H || Wo != W) return fail(MFN_E_SHAPE, "deform_conv_shared_bwd: the flow-shared form needs Ho == H and Wo == W (got %dx%d -> %dx%d)", H, W, Ho, Wo);
+  if (p.Ho != H || p.Wo != W)
+    return fail(MFN_E_SHAPE, "deform_conv_shared_bwd: the flow-shared form needs Ho == H and Wo == W (got %dx%d -> %dx%d)", H, W, p.Ho, p.Wo);
   const size_t ob = dc_shared_bwd_off_bytes(N, H, W, kh, kw);
   if (N != 0 && (!workspace || ws_bytes < 2 * ob || !aligned(workspace, 16)))
     return fail(MFN_E_PARAM, "deform_conv_shared_bwd: workspace of mfn_deform_conv_shared_bwd_workspace_bytes (16-byte aligned) required");
+  if ((rc = dc_bwd_reqs(p))) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  if (N == 0) return dc_bwd_empty(p, s);
   float *off = (float *)workspace, *goff = (float *)((char *)workspace + ob);
-  void *inner = (char *)workspace + 2 * ob;
-  if (dc_bwd_flow_direct(st, x, w, N, Cin, H, W, Cout, kh, kw, ph, pw, dh, dw, groups, req_w, inner, ws_bytes - 2 * ob)) {
-    // the lane = pixel kernels take the flow field itself: no offsets, no per-tap offset gradient (tuning key dc.bwdflow)
-    const DcFlowArgs fl{flow, gflow, flow_scale, flow_stride};
-    return dc_bwd_run(st, gout, x, nullptr, w, gx, nullptr, gw, gbias, N, Cin, H, W, Cout, kh, kw, 1, 1, ph, pw, dh, dw, groups, 1, req_x,
-                      req_flow, req_w, req_bias, inner, ws_bytes - 2 * ob, stream, &fl);
+  void *inner = (char *)workspace + 2 * ob;   // 16-byte aligned, as the workspace is
+  const bool x16 = aligned(x, 16), w16 = aligned(w, 16);
+  const DcBwdPlan pl = dc_bwd_plan(st, p, true, x16, w16, ws_bytes - 2 * ob);
+  if (pl.flow_ok) {   // the lane = pixel kernels take the flow field itself: no offsets, no per-tap offset gradient
+    const DcFlowArgs fl{flow, flow_scale, flow_stride};
+    return hipfail(dc_bwd_exec(pl, p, inner, &fl, s), "deform_conv_bwd");
   }
-  if (N != 0 && (rc = MFN_API(offsets_from_flow)(flow, off, N, H, W, kh * kw, flow_scale, flow_stride, stream))) return rc;
-  rc = MFN_API(deform_conv_bwd)(gout, x, off, w, gx, goff, gw, gbias, N, Cin, H, W, Cout, kh, kw, 1, 1, ph, pw, dh, dw, groups, 1,
-                                req_x, req_flow ? MFN_REQ_WRITE : MFN_REQ_NULL, req_w, req_bias, inner, ws_bytes - 2 * ob, stream);
-  if (rc || N == 0 || !req_flow) return rc;
-  return MFN_API(offsets_from_flow_bwd)(goff, gflow, N, H, W, kh * kw, flow_scale, flow_stride, req_flow, stream);
+  if ((rc = offsets_from_flow_run(st, flow, off, N, H, W, kh * kw, flow_scale, flow_stride, s))) return rc;
+  p.offset = off; p.goffset = goff; p.req_offset = req_flow ? MFN_REQ_WRITE : MFN_REQ_NULL;
+  rc = hipfail(dc_bwd_exec(dc_bwd_plan(st, p, false, x16, w16, ws_bytes - 2 * ob), p, inner, nullptr, s), "deform_conv_bwd");
+  if (rc || !req_flow) return rc;
+  return offsets_from_flow_bwd_run(goff, gflow, N, H, W, kh * kw, flow_scale, flow_stride, req_flow, s);
 }
 
 // ---- Convolution / Deconvolution (SURVEY.md 8 f-4b) ---------------------------------------------------------------
@@ -1335,26 +1382,32 @@ static ConvSetup conv_setup(const Settings &st, int N, int Cin, int H, int W, in
   return cs;
 }
 
+static size_t conv_packed_bytes(const ConvSetup &cs, int Cin, int Cout, int kh, int kw, int groups) {
+  return cs.pl.mfma ? cs.pl.wt_bytes : (((size_t)Cout * (Cin / groups) * kh * kw * sizeof(float)) + 15) / 16 * 16;
+}
 size_t MFN_API(conv2d_packed_weight_bytes)(int N, int Cin, int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph, int pw,
                                            int dh, int dw, int groups, int transposed) {
   int Ho, Wo;
   if (conv_dims("conv2d", N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, transposed, 0, 0, &Ho, &Wo)) return 0;
-  const ConvSetup cs = conv_setup(settings_now(), N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, transposed, 0, 0, Ho, Wo);
-  if (!cs.pl.mfma) return (((size_t)Cout * (Cin / groups) * kh * kw * sizeof(float)) + 15) / 16 * 16;
-  return cs.pl.wt_bytes;
+  return conv_packed_bytes(conv_setup(settings_now(), N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, transposed, 0, 0, Ho, Wo), Cin, Cout,
+                           kh, kw, groups);
+}
+// workspace of a forward call that is given `w` instead of a packed buffer (adj: a Deconvolution's; the size query has none)
+static size_t conv_ws_bytes(const Settings &st, int N, int Cin, int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
+                            int groups, int transposed, int adj_h = 0, int adj_w = 0) {
+  int Ho, Wo;
+  if (conv_dims("conv2d", N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, transposed, adj_h, adj_w, &Ho, &Wo)) return 0;
+  const ConvSetup cs = conv_setup(st, N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, transposed, adj_h, adj_w, Ho, Wo);
+  if (cs.pl.few) return conv_few_workspace_bytes(N, Cin, H, W, Cout);   // partial sums of the channel blocks (coarse levels)
+  if (cs.pl.dcm) {   // a call whose tensors are not 16-byte aligned packs for conv_mfma_kernel instead: room for either
+    const ConvSetup c2 = conv_setup(st, N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, transposed, adj_h, adj_w, Ho, Wo, false);
+    return cs.pl.wt_bytes > c2.pl.wt_bytes ? cs.pl.wt_bytes : c2.pl.wt_bytes;
+  }
+  return cs.pl.mfma ? cs.pl.wt_bytes : 0;   // the re-laid-out weights
 }
 size_t MFN_API(conv2d_workspace_bytes)(int N, int Cin, int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph, int pw,
                                        int dh, int dw, int groups, int transposed) {
-  const Settings st = settings_now();
-  int Ho, Wo;
-  if (conv_dims("conv2d", N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, transposed, 0, 0, &Ho, &Wo)) return 0;
-  const ConvSetup cs = conv_setup(st, N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, transposed, 0, 0, Ho, Wo);
-  if (cs.pl.few) return conv_few_workspace_bytes(N, Cin, H, W, Cout);   // partial sums of the channel blocks (coarse levels)
-  if (cs.pl.dcm) {   // a call whose tensors are not 16-byte aligned packs for conv_mfma_kernel instead: room for either
-    const ConvSetup c2 = conv_setup(st, N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, transposed, 0, 0, Ho, Wo, false);
-    return cs.pl.wt_bytes > c2.pl.wt_bytes ? cs.pl.wt_bytes : c2.pl.wt_bytes;
-  }
-  return cs.pl.mfma ? cs.pl.wt_bytes : 0;   // the re-laid-out weights of a call that is given `w` instead of a packed buffer
+  return conv_ws_bytes(settings_now(), N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, transposed);
 }
 
 int MFN_API(conv2d_pack_weights)(const float *w, int N, int Cin, int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph,
@@ -1366,7 +1419,7 @@ int MFN_API(conv2d_pack_weights)(const float *w, int N, int Cin, int H, int W, i
   if (!w || !packed || !layout_tag) return fail(MFN_E_NULL, "conv2d_pack_weights: NULL pointer");
   if (!aligned(packed, 16)) return fail(MFN_E_ALIGN, "conv2d_pack_weights: packed buffer must be 16-byte aligned");
   const ConvSetup cs = conv_setup(settings_now(), N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, transposed, 0, 0, Ho, Wo);
-  const size_t need = MFN_API(conv2d_packed_weight_bytes)(N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, transposed);
+  const size_t need = conv_packed_bytes(cs, Cin, Cout, kh, kw, groups);
   if (packed_bytes < need) return fail(MFN_E_WORKSPACE, "conv2d_pack_weights: %zu bytes required (got %zu)", need, packed_bytes);
   if (!cs.pl.mfma) {
     *layout_tag = kConvPlainTag;
@@ -1380,13 +1433,12 @@ int MFN_API(conv2d_pack_weights)(const float *w, int N, int Cin, int H, int W, i
   return hipfail(cs.pl.mma ? conv_pack_bf16_launch(pp, (hipStream_t)stream) : conv_pack_launch(pp, (hipStream_t)stream), "conv2d_pack_weights");
 }
 
-int MFN_API(conv2d_fwd)(const float *x, long long in_batch_stride, const float *w_or_null, const void *packed_or_null,
-                        size_t packed_bytes, unsigned long long layout_tag, const float *bias_or_null, float *out,
-                        long long out_batch_stride, int N,
-                        int Cin, int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int groups,
-                        int transposed, int adj_h, int adj_w, int activation, void *workspace, size_t workspace_bytes,
-                        void *stream) {
-  const Settings st = settings_now();
+static int conv_fwd_common(const Settings &st, const float *x, long long in_batch_stride, const float *w_or_null, const void *packed_or_null,
+                           size_t packed_bytes, unsigned long long layout_tag, const float *bias_or_null, float *out,
+                           long long out_batch_stride, int N,
+                           int Cin, int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int groups,
+                           int transposed, int adj_h, int adj_w, int activation, void *workspace, size_t workspace_bytes,
+                           void *stream) {
   const char *what = transposed ? "conv2d_transpose_fwd" : "conv2d_fwd";
   int Ho, Wo;
   int rc = conv_dims(what, N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, transposed, adj_h, adj_w, &Ho, &Wo);
@@ -1515,6 +1567,17 @@ int MFN_API(conv2d_fwd)(const float *x, long long in_batch_stride, const float *
   return hipfail(rc, what);
 }
 
+int MFN_API(conv2d_fwd)(const float *x, long long in_batch_stride, const float *w_or_null, const void *packed_or_null,
+                        size_t packed_bytes, unsigned long long layout_tag, const float *bias_or_null, float *out,
+                        long long out_batch_stride, int N,
+                        int Cin, int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int groups,
+                        int transposed, int adj_h, int adj_w, int activation, void *workspace, size_t workspace_bytes,
+                        void *stream) {
+  return conv_fwd_common(settings_now(), x, in_batch_stride, w_or_null, packed_or_null, packed_bytes, layout_tag, bias_or_null, out,
+                         out_batch_stride, N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, transposed, adj_h, adj_w, activation,
+                         workspace, workspace_bytes, stream);
+}
+
 // ---- backward of the f rows (round 3): Upsample, LeakyReLU, Convolution / Deconvolution -------------------------------
 int MFN_API(upsample_bwd)(const float *gout, float *gx, int N, int C, int H, int W, int factor, int req, void *stream) {
   if (!req_ok(req)) return fail(MFN_E_PARAM, "upsample_bwd: req must be 0 (null), 1 (write) or 3 (add)");
@@ -1538,17 +1601,25 @@ int MFN_API(leaky_relu_bwd)(const float *gout, const float *y, float *gin, size_
   return hipfail(leaky_bwd_launch(LeakyBwdParams{gout, y, gin, n, slope}, (hipStream_t)stream), "leaky_relu_bwd");
 }
 
-// workspace of mfn_conv2d_bwd: [gpre: the gradient before the fused LeakyReLU] [zero offsets of the weight-gradient call]
-// [flipped weights | gx temporary] [inner: the forward call's packed weights, the deformable weight gradient's slabs]
-struct ConvBwdWs { size_t gpre, zoff, wflip, gxtmp, s2d, inner, total; int Ho, Wo; int via_s2d; };
-// the network's transposed convolution (4x4 / stride 2 / pad 1, no adj): its data gradient as a 3x3 convolution of the
-// pixel-unshuffled output gradient (kernels/backward.h conv_s2d_kernel) on the MFMA kernels
-static bool conv_bwd_s2d_shape(const Settings &st, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int transposed, int adj_h, int adj_w) {
-  return transposed && kh == 4 && kw == 4 && sh == 2 && sw == 2 && ph == 1 && pw == 1 && dh == 1 && dw == 1 && !adj_h && !adj_w &&
-         !(st.t.path_generic & 4);
-}
-static int conv_bwd_ws(const Settings &st, ConvBwdWs &q, const char *what, int N, int Cin, int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph,
-                       int pw, int dh, int dw, int groups, int transposed, int adj_h, int adj_w, int activation, int req_x) {
+// What conv_bwd_plan decides for mfn_conv2d_bwd and the call executes.  Workspace: [gpre: the gradient before the fused LeakyReLU]
+// [zero offsets of the weight-gradient call] [flipped weights] [gx temporary] [s2d] [inner: the forward call's packed weights, the
+// weight gradient's slabs]
+enum class ConvBwdData { S2d, Conv, Flip, Deconv };
+struct ConvBwdPlan {
+  size_t gpre, zoff, wflip, gxtmp, s2d, inner, total;
+  int Ho, Wo;
+  // data gradient, a forward call (N, Cin', H', W') -> (N, Cin, H, W).  S2d: the network's transposed convolution (4x4 / stride 2 / pad 1,
+  // no adj) as a 3x3 convolution of the pixel-unshuffled output gradient (kernels/backward.h conv_s2d_kernel) on the MFMA kernels |
+  // Conv: a transposed layer's, Convolution(gpre, w) | Flip: stride 1, convolution of gpre with the flipped, transposed filters |
+  // Deconv: strided, Deconvolution(gpre, w) with THIS call's adj (odd input sizes: adj != 0; the kernel family depends on it)
+  ConvBwdData data;
+  struct { int Cin, H, W, kh, kw, sh, sw, ph, pw, dh, dw, transposed, adj_h, adj_w; } d;
+  bool wgrad_own;   // the convolution's own weight-gradient kernel (conv_wgrad.h); else the deformable weight gradient with zero offsets
+};
+// al16: gpre and x are 16-byte aligned, which conv_wgrad needs and the size query cannot know: the scratch serves either weight gradient
+static int conv_bwd_plan(const Settings &st, ConvBwdPlan &q, const char *what, int N, int Cin, int H, int W, int Cout, int kh, int kw, int sh, int sw,
+                         int ph, int pw, int dh, int dw, int groups, int transposed, int adj_h, int adj_w, int activation, int req_x,
+                         bool al16 = true) {
   memset(&q, 0, sizeof(q));
   int rc = conv_dims(what, N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, transposed, adj_h, adj_w, &q.Ho, &q.Wo);
   if (rc) return rc;
@@ -1560,61 +1631,53 @@ static int conv_bwd_ws(const Settings &st, ConvBwdWs &q, const char *what, int N
   q.zoff = up((size_t)N * 2 * kh * kw * wplane * 4);
   q.wflip = up((size_t)Cout * Cin * kh * kw * 4);
   q.gxtmp = req_x == MFN_REQ_ADD ? up(in_elems * 4) : 0;
-  size_t inner = 0;
-  if (transposed) {   // gx = Convolution(gpre, w): (N,Cout,Ho,Wo) -> (N,Cin,H,W)
-    q.via_s2d = conv_bwd_s2d_shape(st, kh, kw, sh, sw, ph, pw, dh, dw, transposed, adj_h, adj_w) ? 1 : 0;
-    if (q.via_s2d) {
-      q.s2d = up(out_elems * 4);                                  // (N, 4 Cout, H, W)
-      q.wflip = up((size_t)Cin * 4 * Cout * 9 * 4);               // (Cin, 4 Cout, 3, 3)
-      inner = MFN_API(conv2d_workspace_bytes)(N, 4 * Cout, H, W, Cin, 3, 3, 1, 1, 1, 1, 1, 1, 1, 0);
-    } else
-    inner = MFN_API(conv2d_workspace_bytes)(N, Cout, q.Ho, q.Wo, Cin, kh, kw, sh, sw, ph, pw, dh, dw, 1, 0);
-    const size_t wg = MFN_API(deform_conv_bwd_workspace_bytes)(N, Cout, q.Ho, q.Wo, Cin, kh, kw, sh, sw, ph, pw, dh, dw, 1, 1);
-    inner = inner > wg ? inner : wg;
+  q.d = {Cout, q.Ho, q.Wo, kh, kw, sh, sw, ph, pw, dh, dw, 0, 0, 0};
+  size_t wg;
+  if (transposed && kh == 4 && kw == 4 && sh == 2 && sw == 2 && ph == 1 && pw == 1 && dh == 1 && dw == 1 && !adj_h && !adj_w &&
+      !(st.t.path_generic & 4)) {
+    q.data = ConvBwdData::S2d;
+    q.s2d = up(out_elems * 4);                                  // (N, 4 Cout, H, W)
+    q.wflip = up((size_t)Cin * 4 * Cout * 9 * 4);               // (Cin, 4 Cout, 3, 3)
+    q.d = {4 * Cout, H, W, 3, 3, 1, 1, 1, 1, 1, 1, 0, 0, 0};
+  } else if (transposed) q.data = ConvBwdData::Conv;
+  else if (sh == 1 && sw == 1) {
+    q.data = ConvBwdData::Flip;
+    q.d.ph = dh * (kh - 1) - ph; q.d.pw = dw * (kw - 1) - pw;
   } else {
-    const bool s1 = sh == 1 && sw == 1;
-    if (s1) {
-      inner = MFN_API(conv2d_workspace_bytes)(N, Cout, q.Ho, q.Wo, Cin, kh, kw, 1, 1, dh * (kh - 1) - ph, dw * (kw - 1) - pw, dh, dw, 1, 0);
-    } else {
-      // the data gradient of a strided convolution is a Deconvolution with THIS call's adj (odd input sizes: adj != 0), and the
-      // kernel family -- hence the packed layout's size -- depends on adj (conv_kind: 4x4 / stride 2 / pad 1 is kind 3 only for adj 0)
-      const int ah = H - ((q.Ho - 1) * sh - 2 * ph + dh * (kh - 1) + 1), aw = W - ((q.Wo - 1) * sw - 2 * pw + dw * (kw - 1) + 1);
-      int Ho2, Wo2;
-      if (conv_dims(what, N, Cout, q.Ho, q.Wo, Cin, kh, kw, sh, sw, ph, pw, dh, dw, 1, 1, ah, aw, &Ho2, &Wo2) == 0) {
-        const ConvSetup cs = conv_setup(st, N, Cout, q.Ho, q.Wo, Cin, kh, kw, sh, sw, ph, pw, dh, dw, 1, 1, ah, aw, Ho2, Wo2);
-        inner = cs.pl.mfma ? cs.pl.wt_bytes : 0;
-      }
-    }
-    size_t wg = MFN_API(deform_conv_bwd_workspace_bytes)(N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, 1, 1);
+    q.data = ConvBwdData::Deconv;
+    q.d.transposed = 1;
+    q.d.adj_h = H - ((q.Ho - 1) * sh - 2 * ph + dh * (kh - 1) + 1); q.d.adj_w = W - ((q.Wo - 1) * sw - 2 * pw + dw * (kw - 1) + 1);
+  }
+  size_t inner = conv_ws_bytes(st, N, q.d.Cin, q.d.H, q.d.W, Cin, q.d.kh, q.d.kw, q.d.sh, q.d.sw, q.d.ph, q.d.pw, q.d.dh, q.d.dw, 1, q.d.transposed,
+                               q.d.adj_h, q.d.adj_w);
+  if (transposed) wg = dc_bwd_ws_bytes(st, N, Cout, q.Ho, q.Wo, Cin, kh, kw, sh, sw, ph, pw, dh, dw, 1, 1);
+  else {
+    wg = dc_bwd_ws_bytes(st, N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, 1, 1);
     if (conv_wgrad_shape_ok(Cin, Cout, H, W, kh, kw, sh, sw, ph, pw, dh, dw) && !(st.t.path_generic & 4)) {
-      // the convolution's own weight-gradient kernel (conv_wgrad.h) -- taken only when gpre and x are 16-byte aligned as well, which
-      // the size query cannot know: an offset view of x falls back to the deformable kernels, so the scratch serves either path
+      q.wgrad_own = al16;
       size_t slab = conv_wgrad_plan(N, Cin, Cout, H, W).slab_bytes;
       if (conv_wgrad_mma_ok(W, dh)) { const size_t s2 = conv_wgrad_plan(N, Cin, Cout, H, W, true).slab_bytes; slab = slab > s2 ? slab : s2; }
       wg = wg > slab ? wg : slab;
     }
-    inner = inner > wg ? inner : wg;
   }
-  q.inner = up(inner);
+  q.inner = up(inner > wg ? inner : wg);
   q.total = q.gpre + q.zoff + q.wflip + q.gxtmp + q.s2d + q.inner;
   return 0;
 }
 
 size_t MFN_API(conv2d_bwd_workspace_bytes)(int N, int Cin, int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph, int pw,
                                            int dh, int dw, int groups, int transposed, int adj_h, int adj_w, int activation) {
-  ConvBwdWs q;
-  if (N <= 0 || conv_bwd_ws(settings_now(), q, "conv2d_bwd_workspace_bytes", N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, transposed,
-                            adj_h, adj_w, activation, MFN_REQ_ADD))
+  ConvBwdPlan q;
+  if (N <= 0 || conv_bwd_plan(settings_now(), q, "conv2d_bwd_workspace_bytes", N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, transposed,
+                              adj_h, adj_w, activation, MFN_REQ_ADD))
     return 0;
   return q.total;
 }
 
 // Backward of mfn_conv2d_fwd (groups == 1), composed from the library's own kernels:
 //   gpre = gout * LeakyReLU'(y)                                        (activation == MFN_ACT_LEAKY_0_1: y = the forward output)
-//   gx   = Convolution: stride 1 -> convolution of gpre with the flipped, transposed filters (the MFMA kernels);
-//                       strided -> Deconvolution(gpre, w) (same weights read as (in = Cout, out = Cin): generic kernel)
-//          Deconvolution: Convolution(gpre, w) (same weights read as (out = Cin, in = Cout))
-//   gw   = the deformable convolution's weight gradient with zero offsets (bilinear sampling at integer positions is the
+//   gx   = a forward call of the plan's data-gradient route
+//   gw   = conv_wgrad, or the deformable convolution's weight gradient with zero offsets (bilinear sampling at integer positions is the
 //          pixel itself, out-of-range taps are zero in both operators); for the transposed operator the roles of x and gpre swap
 //   gb   = sum of gpre over (n, pixel)
 int MFN_API(conv2d_bwd)(const float *gout, const float *x, const float *w, const float *y_or_null, float *gx, float *gw,
@@ -1626,16 +1689,16 @@ int MFN_API(conv2d_bwd)(const float *gout, const float *x, const float *w, const
   if (!req_ok(req_x) || !req_ok(req_w) || !req_ok(req_bias)) return fail(MFN_E_PARAM, "%s: req must be 0 (null), 1 (write) or 3 (add)", what);
   if (groups != 1) return fail(MFN_E_UNSUPPORTED, "%s: num_group=%d (the reference's blocks use 1)", what, groups);
   if (activation != MFN_ACT_NONE && activation != MFN_ACT_LEAKY_0_1) return fail(MFN_E_PARAM, "%s: unknown activation %d", what, activation);
-  ConvBwdWs q;
-  int rc = conv_bwd_ws(st, q, what, N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, transposed, adj_h, adj_w, activation, req_x);
+  ConvBwdPlan q;   // gpre is gout or the head of the (16-byte aligned) workspace
+  int rc = conv_bwd_plan(st, q, what, N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, transposed, adj_h, adj_w, activation, req_x,
+                         aligned(x, 16) && (activation == MFN_ACT_LEAKY_0_1 || aligned(gout, 16)));
   if (rc) return rc;
   if (!w || (N != 0 && (!gout || !x))) return fail(MFN_E_NULL, "%s: NULL tensor pointer", what);
   if (activation == MFN_ACT_LEAKY_0_1 && N != 0 && !y_or_null) return fail(MFN_E_NULL, "%s: the forward output is needed for the fused LeakyReLU", what);
   if ((N != 0 && req_x && !gx) || (req_w && !gw) || (req_bias && !gbias)) return fail(MFN_E_NULL, "%s: NULL gradient output", what);
   hipStream_t s = (hipStream_t)stream;
-  const size_t wcount = (size_t)Cout * Cin * kh * kw;
   if (N == 0) {
-    if (req_w == MFN_REQ_WRITE && (rc = fill_zero_launch(gw, wcount, s))) return hipfail(rc, what);
+    if (req_w == MFN_REQ_WRITE && (rc = fill_zero_launch(gw, (size_t)Cout * Cin * kh * kw, s))) return hipfail(rc, what);
     if (req_bias == MFN_REQ_WRITE && (rc = fill_zero_launch(gbias, (size_t)Cout, s))) return hipfail(rc, what);
     return 0;
   }
@@ -1656,44 +1719,36 @@ int MFN_API(conv2d_bwd)(const float *gout, const float *x, const float *w, const
     gpre = gpre_buf;
   }
   if (req_x) {
-    float *dst = req_x == MFN_REQ_ADD ? gxtmp : gx;
-    if (transposed && q.via_s2d) {
+    const float *src = gpre, *wsrc = w;
+    if (q.data == ConvBwdData::S2d) {
       const size_t nt = (size_t)N * 4 * Cout * H * W, nw3 = (size_t)Cin * 4 * Cout * 9;
       if ((rc = launch("conv_s2d", conv_s2d_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, s, S2dParams{gpre, s2d, N, Cout, H, W})))
         return hipfail(rc, what);
       if ((rc = launch("conv_s2d_weights", conv_s2d_weights_kernel, dim3((unsigned)((nw3 + 255) / 256)), dim3(256), 0, s,
                        S2dWeightParams{w, wflip, Cin, Cout})))
         return hipfail(rc, what);
-      rc = MFN_API(conv2d_fwd)(s2d, 0, wflip, nullptr, 0, 0, nullptr, dst, 0, N, 4 * Cout, H, W, Cin, 3, 3, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0,
-                               MFN_ACT_NONE, inner, q.inner, stream);
-    } else if (transposed) {
-      rc = MFN_API(conv2d_fwd)(gpre, 0, w, nullptr, 0, 0, nullptr, dst, 0, N, Cout, Ho, Wo, Cin, kh, kw, sh, sw, ph, pw, dh, dw, 1, 0, 0, 0,
-                               MFN_ACT_NONE, inner, q.inner, stream);
-    } else if (sh == 1 && sw == 1) {
+      src = s2d; wsrc = wflip;
+    } else if (q.data == ConvBwdData::Flip) {
       if ((rc = conv_flip_weights_launch(FlipParams{w, wflip, Cout, Cin, kh, kw}, s))) return hipfail(rc, what);
-      rc = MFN_API(conv2d_fwd)(gpre, 0, wflip, nullptr, 0, 0, nullptr, dst, 0, N, Cout, Ho, Wo, Cin, kh, kw, 1, 1, dh * (kh - 1) - ph,
-                               dw * (kw - 1) - pw, dh, dw, 1, 0, 0, 0, MFN_ACT_NONE, inner, q.inner, stream);
-    } else {
-      const int ah = H - ((Ho - 1) * sh - 2 * ph + dh * (kh - 1) + 1), aw = W - ((Wo - 1) * sw - 2 * pw + dw * (kw - 1) + 1);
-      rc = MFN_API(conv2d_fwd)(gpre, 0, w, nullptr, 0, 0, nullptr, dst, 0, N, Cout, Ho, Wo, Cin, kh, kw, sh, sw, ph, pw, dh, dw, 1, 1, ah, aw,
-                               MFN_ACT_NONE, inner, q.inner, stream);
+      wsrc = wflip;
     }
+    rc = conv_fwd_common(st, src, 0, wsrc, nullptr, 0, 0, nullptr, req_x == MFN_REQ_ADD ? gxtmp : gx, 0, N, q.d.Cin, q.d.H, q.d.W, Cin, q.d.kh, q.d.kw,
+                         q.d.sh, q.d.sw, q.d.ph, q.d.pw, q.d.dh, q.d.dw, 1, q.d.transposed, q.d.adj_h, q.d.adj_w, MFN_ACT_NONE, inner, q.inner, stream);
     if (rc) return rc;
     if (req_x == MFN_REQ_ADD && (rc = accumulate_launch(gx, gxtmp, in_elems, s))) return hipfail(rc, what);
   }
-  if (req_w && !transposed && conv_wgrad_shape_ok(Cin, Cout, H, W, kh, kw, sh, sw, ph, pw, dh, dw) && !(st.t.path_generic & 4) &&
-      aligned(gpre, 16) && aligned(x, 16)) {
+  if (req_w && q.wgrad_own) {
     if ((rc = conv_wgrad_launch(gpre, x, gw, inner, N, Cin, Cout, H, W, dh, req_w == MFN_REQ_ADD ? 1 : 0, s, st.conv != 0))) return hipfail(rc, what);
   } else if (req_w) {
     const size_t wplane = transposed ? (size_t)H * W : (size_t)Ho * Wo;
     if ((rc = fill_zero_launch(zoff, (size_t)N * 2 * kh * kw * wplane, s))) return hipfail(rc, what);
     // (gout', x') of the deformable weight gradient: Convolution (gpre, x); Deconvolution (x, gpre) -- gw comes out as
     // (Cout, Cin, kh, kw) resp. (Cin, Cout, kh, kw), the operators' own layouts
-    rc = transposed ? MFN_API(deform_conv_bwd)(x, gpre, zoff, w, nullptr, nullptr, gw, nullptr, N, Cout, Ho, Wo, Cin, kh, kw, sh, sw, ph, pw,
-                                               dh, dw, 1, 1, MFN_REQ_NULL, MFN_REQ_NULL, req_w, MFN_REQ_NULL, inner, q.inner, stream)
-                    : MFN_API(deform_conv_bwd)(gpre, x, zoff, w, nullptr, nullptr, gw, nullptr, N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw,
-                                               dh, dw, 1, 1, MFN_REQ_NULL, MFN_REQ_NULL, req_w, MFN_REQ_NULL, inner, q.inner, stream);
-    if (rc) return rc;
+    const DcBwdParams wp = transposed ? DcBwdParams{x, gpre, zoff, w, nullptr, nullptr, gw, nullptr, N, Cout, Ho, Wo, Cin, 0, 0, kh, kw, sh, sw, ph, pw,
+                                                    dh, dw, 1, 1, MFN_REQ_NULL, MFN_REQ_NULL, req_w, MFN_REQ_NULL, 1}
+                                      : DcBwdParams{gpre, x, zoff, w, nullptr, nullptr, gw, nullptr, N, Cin, H, W, Cout, 0, 0, kh, kw, sh, sw, ph, pw,
+                                                    dh, dw, 1, 1, MFN_REQ_NULL, MFN_REQ_NULL, req_w, MFN_REQ_NULL, 1};
+    if ((rc = dc_bwd_run(st, wp, inner, q.inner, s))) return rc;
   }
   if (req_bias) {
     // slices of the (n, pixel) range over blockIdx.y; their partial sums sit in the zero-offset buffer, which is free by now

@@ -29,7 +29,7 @@
 //                 (forward and backward), 4 = convolution
 //   bwd.off       bits that switch backward kernels off: 1 = the lane = pixel shared-offset input / offset gradient (tap by tap
 //                 only), 2 = flow mode (mfn_deform_conv_shared_bwd then always composes: offsets into the workspace ->
-//                 mfn_deform_conv_bwd -> sum of the taps' offset gradients), 4 = corr_bwd_lds_kernel (corr_bwd_block_kernel at
+//                 the plan of mfn_deform_conv_bwd -> sum of the taps' offset gradients), 4 = corr_bwd_lds_kernel (corr_bwd_block_kernel at
 //                 every level)
 //   conv.mt / conv.pt  32-filter tiles per wave (1..4) / pixel tiles per block (4, or 1 = four in-block K slices); 0 = plan (the plan
 //                 only picks pt = 4 and mt > 2 for images of >= 1024 pixel tiles: the CPU emulation tests reach those kernels through these)

@@ -282,3 +282,31 @@ def test_every_kernel_is_reachable_from_the_c_abi():
                 todo.extend(bodies.get(name, []))
     missing = sorted(kernels - reached)
     assert not missing, "kernels no exported function can reach: %s" % missing
+
+
+def test_exported_entries_do_not_call_each_other_and_read_the_settings_once():
+    """Inside api_impl.inc no exported function calls another exported function, the pure *_out_shape ones excepted (an inner exported
+    call would validate again and take its own reading of the process-wide settings), and settings_now() is read at most once per
+    exported entry and nowhere else: a call is sized, planned and run under one set of values."""
+    import re
+    api = open(os.path.join(ROOT, "maskflownet_amd", "csrc", "api_impl.inc")).read()
+    api = re.sub(r"//[^\n]*", "", api)
+    exported, spans = {}, []
+    for m in re.finditer(r"MFN_API\(([a-z0-9_]+)\)\s*\([^)]*\)\s*\{", api):
+        b, depth = m.end(), 1
+        while b < len(api) and depth:
+            depth += api[b] == "{"
+            depth -= api[b] == "}"
+            b += 1
+        exported[m.group(1)] = api[m.end():b]
+        spans.append((m.end(), b))
+    assert len(exported) >= 40, len(exported)
+    for name, body in exported.items():
+        inner = [c for c in re.findall(r"MFN_API\(([a-z0-9_]+)\)", body) if not c.endswith("_out_shape")]
+        assert not inner, "%s calls the exported %s" % (name, inner)
+        assert body.count("settings_now()") <= 1, name
+    outside = "".join(api[a:b] for a, b in zip([0] + [e for _, e in spans], [s for s, _ in spans] + [len(api)]))
+    assert outside.count("settings_now()") == 1, "settings_now() is read outside the exported entries"   # its definition
+    # the static helpers call no exported function but the *_out_shape ones (the rest of the mentions are the definitions' heads)
+    heads = re.sub(r"MFN_API\(([a-z0-9_]+)\)\s*\([^)]*\)\s*\{", "", outside)
+    assert all(c.endswith("_out_shape") for c in re.findall(r"MFN_API\(([a-z0-9_]+)\)", heads)), heads
