@@ -310,3 +310,52 @@ def warp_backward_bound(gout, x, flow_yx, clip_grid=False, positions_dtype=np.fl
     """M of Reconstruction2D[Smooth]'s backward: (Mgx, Mgflow), at the sample positions the grid arithmetic gives in
     `positions_dtype` (float64: the fp64 oracle's; float32: the fp32 kernels' and the fp32 oracle's)."""
     return warp_backward_at(gout, x, warp_positions(flow_yx, clip_grid, positions_dtype), bound=True)
+
+
+# ---- magnitude bounds of the forward pass ------------------------------------------------------------------------------------
+# M as above, per output element.  Every forward operator here is a sum of products whose interpolation weights are >= 0, so M is
+# the operator itself on the absolute values of its inputs, at the SAME sample positions.  A fused LeakyReLU is 1-Lipschitz and
+# keeps zeros: its output is compared with leaky(want64) under the same M.
+def correlation_bound(f1, f2, max_displacement=4):
+    """M of Correlation (kernel 1, strides 1, pad = md, multiply): the cost volume of |f1|, |f2|; zero exactly where the
+    displacement leaves the image."""
+    return correlation(np.abs(np.asarray(f1, np.float64)), np.abs(np.asarray(f2, np.float64)), max_displacement)
+
+
+def deformable_convolution_bound(x, offset, weight, bias=None, kernel=(3, 3), stride=(1, 1), dilate=(1, 1), pad=(1, 1),
+                                 num_group=1, num_deformable_group=1):
+    """M of DeformableConvolution: the operator on |x|, |W|, |b| at the same offsets (the bilinear weights are >= 0); without a
+    bias, zero exactly where every tap of an output falls outside the image."""
+    return deformable_convolution(np.abs(np.asarray(x, np.float64)), offset, np.abs(np.asarray(weight, np.float64)),
+                                  None if bias is None else np.abs(np.asarray(bias, np.float64)), kernel, stride, dilate, pad,
+                                  num_group, num_deformable_group)
+
+
+def matching_bound(m_dc, mask=None, tradeoff=None):
+    """M of the matching epilogue deform * sigmoid(mask) + tradeoff: M_dc * sigmoid(mask) + |tradeoff|."""
+    m = np.asarray(m_dc, np.float64)
+    if mask is not None:
+        m = m * (1.0 / (1.0 + np.exp(-np.asarray(mask, np.float64))))
+    if tradeoff is not None:
+        m = m + np.abs(np.asarray(tradeoff, np.float64))
+    return m
+
+
+def warp_at(x, positions, bound=False):
+    """fp64 BilinearSampler forward at given sample positions (warp_positions): the forward twin of warp_backward_at.  Corners
+    outside the image contribute nothing.  bound=True: the magnitude bound M, the same sum on |x|."""
+    x_all = np.asarray(x, np.float64)
+    if bound:
+        x_all = np.abs(x_all)
+    yr_all, xr_all = positions[0], positions[1]
+    N, C, H, W = x_all.shape
+    out = np.zeros((N, C) + yr_all.shape[1:])
+    for n in range(N):
+        yr, xr = yr_all[n], xr_all[n]
+        y0 = np.floor(yr).astype(np.int64)
+        x0 = np.floor(xr).astype(np.int64)
+        wy = 1.0 - (yr - y0)
+        wx = 1.0 - (xr - x0)
+        for dy, dx, wgt in ((0, 0, wy * wx), (0, 1, wy * (1 - wx)), (1, 0, (1 - wy) * wx), (1, 1, (1 - wy) * (1 - wx))):
+            out[n] += _tap(x_all[n], y0 + dy, x0 + dx) * wgt[None]
+    return out

@@ -574,6 +574,22 @@ def graded_gout(rng, shape):
     return g.astype(np.float32)
 
 
+def graded_feat(rng, shape, kind):
+    """Forward twin of graded_gout.  'plain': feat().  'graded-pixel': feat() scaled per pixel by 10**U(-6, 0), the first image as a
+    whole by 1e-3 -- a pyramid level has quiet and loud regions orders of magnitude apart.  'graded-channel': scaled per channel by
+    10**U(-6, 0).  Everything stays far inside the normal fp32 range (products >= ~1e-13 of a plain product)."""
+    x = feat(rng, shape).astype(np.float64)
+    N, C, H, W = shape
+    if kind == "graded-pixel":
+        x *= 10.0 ** rng.uniform(-6.0, 0.0, (N, 1, H, W))
+        x[0] *= 1e-3
+    elif kind == "graded-channel":
+        x *= 10.0 ** rng.uniform(-6.0, 0.0, (1, C, 1, 1))
+    else:
+        assert kind == "plain", kind
+    return x.astype(np.float32)
+
+
 def check_fp64_bound(got, want64, ref32, M, what="", base=None):
     """The backward acceptance rule: per element e = |got - want64| / M (M: oracle/ref_numpy.*_bound).
       bound             max e_lib <= 4 * max e_ref32 + 16 * 2^-24 over the elements with M > 0;

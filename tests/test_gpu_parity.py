@@ -5,7 +5,9 @@ import ctypes
 import numpy as np
 import pytest
 
+from oracle import ref_numpy
 from tests import parity_cases as pc
+from tests.fp64_env import exact_positions
 
 pytestmark = pytest.mark.gpu
 
@@ -149,6 +151,13 @@ def test_correlation_numeric_range_edge_cases(ops, oracle, dev):
     f1, f2 = pc.feat(rng, shape), pc.feat(rng, shape)
     mag = (10.0 ** np.linspace(-18, 18, 32)).astype(np.float32)[None, :, None, None]
     f1r, f2r = (f1 * mag).astype(np.float32), (f2 * mag).astype(np.float32)
+    # per element against the fp64 oracle (tests/test_forward_fp64.py's rule), on the normal-range features: the maximum norm below
+    # only sees the largest channel
+    want64, M = oracle.correlation(f1r, f2r, max_displacement=4, pad_size=4, dtype=np.float64), ref_numpy.correlation_bound(f1r, f2r, 4)
+    ref32 = oracle.correlation(f1r, f2r, max_displacement=4, pad_size=4)
+    for arith in (0, -1):
+        _lib.set_tuning(corr_gram=arith)
+        pc.check_fp64_bound(host(ops.Correlation(dev(f1r), dev(f2r), 1, 4, 1, 1, 4)), want64, ref32, M, what="wide dynamic range, arithmetic %d" % arith)
     f1r[0, :, 3, 5] = np.float32(1e-41)      # denormals
     f2r[1, 4, 7, 9] = np.float32(-3e-42)
     for arith in (0, -1):
@@ -248,6 +257,15 @@ def test_deform_numeric_range_edge_cases(ops, oracle, dev):
     off = oracle.offsets_from_flow(fl, 20.0, 4.0)
     mag = (10.0 ** np.linspace(-12, 12, C)).astype(np.float32)[None, :, None, None]
     xr = (x * mag).astype(np.float32)
+    # per element against the fp64 oracle (tests/test_forward_fp64.py's rule), on the normal-range features and with the offsets on the
+    # grid where fp32 sample positions are exact: the maximum norm below only sees the largest channel
+    off_e = exact_positions(off)
+    want64, M = oracle.deformable_convolution(xr, off_e, w, b, kernel=(3, 3), pad=(1, 1), dtype=np.float64), ref_numpy.deformable_convolution_bound(xr, off_e, w, b)
+    ref32 = oracle.deformable_convolution(xr, off_e, w, b, kernel=(3, 3), pad=(1, 1))
+    for arith in (0, -1):
+        _lib.set_arithmetic(deformable_convolution=arith)
+        got = host(ops.DeformableConvolution(dev(xr), dev(off_e), dev(w), dev(b), kernel=(3, 3), pad=(1, 1), num_filter=C))
+        pc.check_fp64_bound(got, want64, ref32, M, what="wide dynamic range, arithmetic %d" % arith)
     xr[0, :, 3, 5] = np.float32(1e-41)       # denormals
     xr[1, 4, 7, 9] = np.float32(-3e-42)
     want = oracle.deformable_convolution(xr, off, w, b, kernel=(3, 3), pad=(1, 1))

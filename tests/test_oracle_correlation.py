@@ -132,3 +132,19 @@ def test_backward_bound_covers_the_fp64_gradient(oracle, shape, md):
         pc.assert_magnitude_bound(m, r, nm)
         np.testing.assert_allclose(m, a, rtol=1e-12, atol=1e-12 * np.abs(a).max(), err_msg=nm)
     assert (M[0] == 0).any()
+
+
+@pytest.mark.parametrize("shape,md", [((2, 3, 5, 7), 4), ((1, 4, 9, 6), 2), ((1, 2, 1, 3), 4)])
+def test_forward_bound_covers_the_fp64_cost_volume(oracle, shape, md):
+    """ref_numpy.correlation_bound: M >= |fp64 cost volume|, zero only where the cost volume is -- exactly the displacements that
+    leave the image --, equal to the C oracle's cost volume of |f1|, |f2|."""
+    rng = np.random.default_rng(23 + md)
+    f1, f2 = rng.standard_normal(shape).astype(np.float32), rng.standard_normal(shape).astype(np.float32)
+    want = oracle.correlation(f1, f2, max_displacement=md, pad_size=md, dtype=np.float64)
+    M = ref_numpy.correlation_bound(f1, f2, md)
+    pc.assert_magnitude_bound(M, want, "cost volume")
+    a = oracle.correlation(np.abs(f1), np.abs(f2), max_displacement=md, pad_size=md, dtype=np.float64)
+    np.testing.assert_allclose(M, a, rtol=1e-12, atol=1e-12 * np.abs(a).max())
+    N, C, H, W = shape
+    outside = sum(H * W - max(H - abs(dy), 0) * max(W - abs(dx), 0) for dy in range(-md, md + 1) for dx in range(-md, md + 1))
+    assert int((M == 0).sum()) == N * outside > 0

@@ -201,3 +201,28 @@ def test_backward_bound_covers_the_fp64_gradient(oracle, shared):
     abs_want = oracle.deformable_convolution_backward(np.abs(go), ax, off, aw, dtype=np.float64)
     for k, nm in ((0, "gx"), (2, "gw"), (3, "gbias")):
         np.testing.assert_allclose(M[k], abs_want[k], rtol=1e-12, atol=1e-12 * np.abs(abs_want[k]).max(), err_msg=nm)
+
+
+@pytest.mark.parametrize("bias", [False, True])
+def test_forward_bound_covers_the_fp64_output(oracle, bias):
+    """ref_numpy.deformable_convolution_bound: M >= |fp64 output|, zero only where the output is (without a bias: the pixels whose
+    taps all fall outside), equal to the C oracle on |x|, |W|, |b|; ref_numpy.matching_bound covers the matching epilogue."""
+    rng = np.random.default_rng(43 + bias)
+    N, Cin, Cout, H, W = 2, 3, 4, 6, 9
+    x, w, b = _case(9 + bias, N=N, Cin=Cin, Cout=Cout, H=H, W=W)
+    b = b if bias else None
+    off = _bound_offsets(rng, N, H, W)
+    off[:, :, 3, 4] = np.float32(-50.0)                       # every tap of this pixel outside
+    want = oracle.deformable_convolution(x, off, w, b, dtype=np.float64)
+    M = ref_numpy.deformable_convolution_bound(x, off, w, b)
+    pc.assert_magnitude_bound(M, want, "output")
+    a = oracle.deformable_convolution(np.abs(x), off, np.abs(w), None if b is None else np.abs(b), dtype=np.float64)
+    np.testing.assert_allclose(M, a, rtol=1e-12, atol=1e-12 * np.abs(a).max())
+    assert ((M == 0).any()) == (not bias)
+    if not bias:
+        assert (M[:, :, 3, 4] == 0).all() and (M[:, :, 0, 0] == 0).all()
+    mask = rng.standard_normal((N, 1, H, W)) * 2
+    tr = rng.standard_normal((N, Cout, H, W))
+    tr[:, :, 3, 4] = 0.0
+    pc.assert_magnitude_bound(ref_numpy.matching_bound(M, mask, tr), want / (1 + np.exp(-mask)) + tr, "matching")
+    pc.assert_magnitude_bound(ref_numpy.matching_bound(M, None, tr), want + tr, "matching, no mask")

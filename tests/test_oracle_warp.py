@@ -155,3 +155,30 @@ def test_backward_at_positions_is_the_fp64_oracle(oracle, clip):
     for g, w, m, nm in zip(got, want, M, ("gx", "gflow")):
         assert (np.abs(g - w) <= 1e-12 * m).all(), nm
         assert not g[m == 0].any() and not w[m == 0].any(), nm
+
+
+@pytest.mark.parametrize("clip", [False, True])
+def test_forward_at_fp32_positions_and_its_bound(oracle, clip):
+    """ref_numpy.warp_at: at the fp64 sample positions it is the fp64 C oracle's warp; at the fp32 positions (the kernels' and the
+    fp32 oracle's) it differs from the fp32 oracle by arithmetic only.  Its bound M >= |result|, zero only where the result is:
+    samples with every corner outside, or whose only corners inside have weight zero."""
+    rng = np.random.default_rng(9 + clip)
+    N, C, H, W = 2, 3, 6, 9
+    x = rng.standard_normal((N, C, H, W)).astype(np.float32)
+    fl = (rng.standard_normal((N, 2, H, W)) * 2.0).astype(np.float32)
+    fl[:, :, ::2] = np.round(fl[:, :, ::2])
+    fl[:, 0, 1, :3] = np.float32(-1.5)            # half above the top border
+    fl[:, 0, 1, 3:5] = np.float32(-3.5)           # above it altogether
+    fl[:, 1, 3, -2:] = np.float32(0.5)            # across the right border
+    fl[:, :, 4, 4] = np.float32(1e4)              # far outside
+    want = oracle.warp(x, fl, clip_grid=clip, dtype=np.float64)
+    p64 = ref_numpy.warp_positions(fl, clip, np.float64)
+    np.testing.assert_allclose(ref_numpy.warp_at(x, p64), want, rtol=0, atol=1e-12)
+    pc.assert_magnitude_bound(ref_numpy.warp_at(x, p64, bound=True), want, "warp at fp64 positions")
+    p32 = ref_numpy.warp_positions(fl, clip, np.float32)
+    at32, M = ref_numpy.warp_at(x, p32), ref_numpy.warp_at(x, p32, bound=True)
+    pc.assert_magnitude_bound(M, at32, "warp at fp32 positions")
+    assert ((M == 0).any()) == (not clip)
+    got32 = oracle.warp(x, fl, clip_grid=clip).astype(np.float64)
+    assert not (got32[M == 0] != 0).any()
+    assert (np.abs(got32 - at32)[M > 0] / M[M > 0]).max() < 8 * 2.0 ** -24
