@@ -265,6 +265,42 @@ int mfn_offsets_from_flow(const float *flow_yx, float *offset, int N, int H, int
                           float scale, float stride, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Prediction on images of any size -- replace the device side of PipelineFlownet in
+ * /root/reference/network/pipeline.py: centralize (:85-87), do_batch_mx (:117-132), do_batch (:134-147) and the
+ * metrics of validate (:176-182).  maskflownet_amd/predict.py composes them around the network's hipGraph.
+ *
+ * [MXNet-ext, unpinned] contrib.BilinearResize2D of MXNet 1.5 (bilinear_resize.cc, align_corners), per axis:
+ *   r = (out > 1) ? (float)(in-1)/(float)(out-1) : 0.f;  p = r * (float)o;  i0 = (int)p;  ip = (i0 < in-1) ? 1 : 0;
+ *   l1 = p - (float)i0;  l0 = 1.f - l1;
+ *   out = h0*(w0*x[i0][j0] + w1*x[i0][j0+jp]) + h1*(w0*x[i0+ip][j0] + w1*x[i0+ip][j0+jp])
+ * with positions, lambdas and the blend in fp32, every operation rounded separately; equal sizes copy.
+ *
+ * The two reductions (joint mean, metrics) run in a fixed order through the caller's workspace, without atomics: results
+ * are bit-identical from run to run and no term passes through more than 46 additions, so that
+ * |result - exact| <= 64 * 2^-24 * sum |terms| (/ n for the mean).  A missing or too small workspace is MFN_E_WORKSPACE. */
+/* rgb_mean of pipeline.py:86: mean[n,c] = (sum im1[n,c] + sum im2[n,c]) / (2 H W); im1, im2: (N,C,H,W), mean: (N,C). */
+size_t mfn_pair_mean_workspace_bytes(int N, int C, int H, int W);
+int mfn_pair_mean(const float *im1, const float *im2, float *mean, int N, int C, int H, int W, void *workspace,
+                  size_t workspace_bytes, void *stream);
+/* pipeline.py:120, :129-130 in one launch: out[0:N] = resize(im1 - mean), out[N:2N] = resize(im2 - mean);
+ * out: (2N,C,Hout,Wout), the network's input batch.  The mean is subtracted from every tap before the blend (the
+ * reference's order: centralize, then resize); Hout == H and Wout == W gives exactly x - mean. */
+int mfn_preprocess_pair(const float *im1, const float *im2, const float *mean, float *out, int N, int C, int H, int W,
+                        int Hout, int Wout, void *stream);
+/* contrib.BilinearResize2D (pipeline.py:129-130, :140, :142): x (N,C,Hin,Win) -> out (N,C,Hout,Wout).
+ * sub_or_null: (N,C), subtracted from every tap before the blend.  flow_rescale != 0 (C == 2, else MFN_E_SHAPE): channel 0
+ * * (float)((double)Hout/Hin), channel 1 * (float)((double)Wout/Win) after the blend, one rounding (pipeline.py:140-141). */
+int mfn_bilinear_resize_fwd(const float *x, const float *sub_or_null, float *out, int N, int C, int Hin, int Win, int Hout,
+                            int Wout, int flow_rescale, void *stream);
+/* EpeLossWithMask (/root/reference/network/MaskFlownet.py:576-583, pipeline.py:146) and the KITTI outlier ratio
+ * (pipeline.py:182) as sums; the caller divides.  flow, label: (N,2,H,W) in network order (channel 0 = dy), mask: (N,1,H,W).
+ * sums (N,3): sum mask * sqrt(|flow-label|^2 + 1e-8), sum mask,
+ *             sum mask * [|flow-label| > 3 and |flow-label| / (|label| + 1e-8) > 0.05],  |v| = sqrt(v_y^2 + v_x^2). */
+size_t mfn_flow_metrics_workspace_bytes(int N, int H, int W);
+int mfn_flow_metrics(const float *flow, const float *label, const float *mask, float *sums, int N, int H, int W,
+                     void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Convolution / Deconvolution -- replace the Gluon blocks of
  * /root/reference/network/MaskFlownet.py:79-163: nn.Conv2D(channels, kernel_size=3, strides, padding, dilation)
  * [+ LeakyReLU(0.1)] of conv() / predict_flow() / predict_mask() (:165-191) and nn.Conv2DTranspose(channels, 4, 2, 1)

@@ -75,6 +75,13 @@ PRODUCT_ONLY = {
     "profile_tag": (_i, [C.c_char_p]),
     "profile_query": (_i, [C.c_char_p, _pi, C.POINTER(C.c_double)]),
     "profile_dump": (_i, [C.c_char_p, _i]),
+    # prediction on images of any size (kernels/predict.h): the oracle has no twin of these, so the emulation build binds none
+    "pair_mean_workspace_bytes": (C.c_size_t, [_i] * 4),
+    "pair_mean": (_i, [_f, _f, _f] + [_i] * 4 + [C.c_void_p, C.c_size_t, _s]),
+    "preprocess_pair": (_i, [_f, _f, _f, _f] + [_i] * 6 + [_s]),
+    "bilinear_resize_fwd": (_i, [_f, _f, _f] + [_i] * 7 + [_s]),
+    "flow_metrics_workspace_bytes": (C.c_size_t, [_i] * 3),
+    "flow_metrics": (_i, [_f, _f, _f, _f] + [_i] * 3 + [C.c_void_p, C.c_size_t, _s]),
 }
 
 

@@ -18,6 +18,7 @@
 #include "kernels/deform_conv_mma.h"
 #include "kernels/warp.h"
 #include "kernels/upsample.h"
+#include "kernels/predict.h"
 #include "kernels/backward.h"
 #include "kernels/dc_backward.h"
 #include "kernels/conv.h"
@@ -815,6 +816,97 @@ int MFN_API(upsample_fwd)(const float *x, float *out, int N, int C, int H, int W
   if (N == 0) return 0;
   UpsampleParams p{x, out, N, C, H, W, factor, store_policy_for(settings_now(), (size_t)N * C * H * W * factor * factor * 4, 2, -1)};
   return hipfail(upsample_launch(p, (hipStream_t)stream), "upsample_fwd");
+}
+
+// ---- prediction on images of any size: joint mean, centralize + resize, metrics (kernels/predict.h) -------------------
+// sizes every resize entry accepts: positive, planes and output elements inside what one launch indexes
+static int resize_dims(const char *what, int N, int C, int Hin, int Win, int Hout, int Wout) {
+  if (N < 0 || C <= 0 || Hin <= 0 || Win <= 0 || Hout <= 0 || Wout <= 0)
+    return fail(MFN_E_SHAPE, "%s: N=%d C=%d Hin=%d Win=%d Hout=%d Wout=%d", what, N, C, Hin, Win, Hout, Wout);
+  if ((size_t)2 * N * C >= ((size_t)1 << 31) || (size_t)Hin * Win >= ((size_t)1 << 31) ||
+      (size_t)2 * N * C * Hout * Wout >= ((size_t)1 << 32))
+    return fail(MFN_E_UNSUPPORTED, "%s: tensor too large", what);
+  return 0;
+}
+static int resize_run(const Settings &st, const char *what, const float *x, const float *x2, const float *sub, float *out, int planes,
+                      int planes_a, int Hin, int Win, int Hout, int Wout, int flow, hipStream_t s) {
+  ResizeParams p{};
+  p.x = x; p.x2 = x2; p.sub = sub; p.out = out;
+  p.planes = planes; p.planes_a = planes_a;
+  p.Hin = Hin; p.Win = Win; p.Hout = Hout; p.Wout = Wout;
+  p.ry = Hout > 1 ? (float)(Hin - 1) / (float)(Hout - 1) : 0.f;
+  p.rx = Wout > 1 ? (float)(Win - 1) / (float)(Wout - 1) : 0.f;
+  p.flow = flow;
+  p.sy = (float)((double)Hout / (double)Hin);
+  p.sx = (float)((double)Wout / (double)Win);
+  p.st_policy = store_policy_for(st, (size_t)planes * Hout * Wout * 4, 2, -1);
+  return hipfail(resize_launch(p, s), what);
+}
+// the reductions' shapes: slices of 4096 elements, at most 4096 of them per result, results over blockIdx.y
+static int reduce_dims(const char *what, size_t results, size_t elems) {
+  if (results > 65535 || (elems + PRED_SLICE - 1) / PRED_SLICE > (size_t)PRED_MAX_SLICES) return fail(MFN_E_UNSUPPORTED, "%s: tensor too large", what);
+  return 0;
+}
+
+size_t MFN_API(pair_mean_workspace_bytes)(int N, int C, int H, int W) {
+  if (N <= 0 || C <= 0 || H <= 0 || W <= 0) return 0;
+  return (size_t)N * C * pred_slices((size_t)2 * H * W) * sizeof(float);
+}
+
+int MFN_API(pair_mean)(const float *im1, const float *im2, float *mean, int N, int C, int H, int W, void *workspace,
+                       size_t workspace_bytes, void *stream) {
+  if (N != 0 && (!im1 || !im2 || !mean)) return fail(MFN_E_NULL, "pair_mean: NULL tensor pointer");
+  if (N < 0 || C <= 0 || H <= 0 || W <= 0) return fail(MFN_E_SHAPE, "pair_mean: N=%d C=%d H=%d W=%d", N, C, H, W);
+  if (N == 0) return 0;
+  const size_t plane = (size_t)H * W;
+  if (int rc = reduce_dims("pair_mean", (size_t)N * C, 2 * plane)) return rc;
+  const int slices = pred_slices(2 * plane);
+  const size_t need = (size_t)N * C * slices * sizeof(float);
+  if (!workspace || workspace_bytes < need)
+    return fail(MFN_E_WORKSPACE, "pair_mean: workspace of %zu bytes needed, %zu given", need, workspace ? workspace_bytes : (size_t)0);
+  if (!aligned(workspace, 4)) return fail(MFN_E_ALIGN, "pair_mean: workspace must be 4-byte aligned");
+  PairMeanParams p{im1, im2, (float *)workspace, mean, plane, N * C, slices,
+                   (plane % 4 == 0 && aligned(im1, 16) && aligned(im2, 16)) ? 1 : 0};
+  return hipfail(pair_mean_launch(p, (hipStream_t)stream), "pair_mean");
+}
+
+int MFN_API(preprocess_pair)(const float *im1, const float *im2, const float *mean, float *out, int N, int C, int H, int W,
+                             int Hout, int Wout, void *stream) {
+  if (N != 0 && (!im1 || !im2 || !mean || !out)) return fail(MFN_E_NULL, "preprocess_pair: NULL tensor pointer");
+  if (int rc = resize_dims("preprocess_pair", N, C, H, W, Hout, Wout)) return rc;
+  if (N == 0) return 0;
+  return resize_run(settings_now(), "preprocess_pair", im1, im2, mean, out, 2 * N * C, N * C, H, W, Hout, Wout, 0, (hipStream_t)stream);
+}
+
+int MFN_API(bilinear_resize_fwd)(const float *x, const float *sub_or_null, float *out, int N, int C, int Hin, int Win, int Hout,
+                                 int Wout, int flow_rescale, void *stream) {
+  if (N != 0 && (!x || !out)) return fail(MFN_E_NULL, "bilinear_resize_fwd: NULL tensor pointer");
+  if (int rc = resize_dims("bilinear_resize_fwd", N, C, Hin, Win, Hout, Wout)) return rc;
+  if (flow_rescale && C != 2) return fail(MFN_E_SHAPE, "bilinear_resize_fwd: flow_rescale needs C == 2 (dy, dx), got C=%d", C);
+  if (N == 0) return 0;
+  return resize_run(settings_now(), "bilinear_resize_fwd", x, nullptr, sub_or_null, out, N * C, N * C, Hin, Win, Hout, Wout,
+                    flow_rescale ? 1 : 0, (hipStream_t)stream);
+}
+
+size_t MFN_API(flow_metrics_workspace_bytes)(int N, int H, int W) {
+  if (N <= 0 || H <= 0 || W <= 0) return 0;
+  return (size_t)N * pred_slices((size_t)H * W) * 3 * sizeof(float);
+}
+
+int MFN_API(flow_metrics)(const float *flow, const float *label, const float *mask, float *sums, int N, int H, int W,
+                          void *workspace, size_t workspace_bytes, void *stream) {
+  if (N != 0 && (!flow || !label || !mask || !sums)) return fail(MFN_E_NULL, "flow_metrics: NULL tensor pointer");
+  if (N < 0 || H <= 0 || W <= 0) return fail(MFN_E_SHAPE, "flow_metrics: N=%d H=%d W=%d", N, H, W);
+  if (N == 0) return 0;
+  const size_t plane = (size_t)H * W;
+  if (int rc = reduce_dims("flow_metrics", N, plane)) return rc;
+  const int slices = pred_slices(plane);
+  const size_t need = (size_t)N * slices * 3 * sizeof(float);
+  if (!workspace || workspace_bytes < need)
+    return fail(MFN_E_WORKSPACE, "flow_metrics: workspace of %zu bytes needed, %zu given", need, workspace ? workspace_bytes : (size_t)0);
+  if (!aligned(workspace, 4)) return fail(MFN_E_ALIGN, "flow_metrics: workspace must be 4-byte aligned");
+  FlowMetricsParams p{flow, label, mask, (float *)workspace, sums, plane, N, slices};
+  return hipfail(flow_metrics_launch(p, (hipStream_t)stream), "flow_metrics");
 }
 
 // ---- backward (SURVEY.md 8 a7) -------------------------------------------------------------------------------

@@ -130,7 +130,8 @@ class MaskFlownetS:
     def __init__(self, params, batch, H, W, device="cuda:0"):
         import torch
         if H % 64 or W % 64:
-            raise ValueError("MaskFlownetS: H and W must be multiples of 64 (the pipeline resizes to that, pipeline.py:139-147)")
+            raise ValueError("MaskFlownetS: H and W must be multiples of 64 (the pipeline resizes to that, pipeline.py:139-147): "
+                             "use maskflownet_amd.predict.Predictor")
         self.torch, self.ops = torch, default_ops()
         self.dev = torch.device(device)
         self.N, self.H, self.W = int(batch), int(H), int(W)

@@ -451,6 +451,78 @@ class OpSet:
         self.check(self.ns.upsample_fwd(self.ad.ptr(x), self.ad.ptr(out), N, C, H, W, factor, self.ad.stream(x)))
         return out
 
+    # ---- prediction on images of any size (network/pipeline.py:85-87, :117-147, :176-182) ---------------------------------
+    def bilinear_resize(self, data, height, width, sub=None, flow_rescale=False, out=None):
+        """contrib.BilinearResize2D(data, height, width) of MXNet 1.5 (align_corners; pipeline.py:129-130, :140, :142):
+        (N,C,Hin,Win) -> (N,C,height,width), positions and blend in fp32.  sub (N,C): subtracted from every tap before the
+        blend (centralize, then resize).  flow_rescale (C == 2): channel 0 * height/Hin, channel 1 * width/Win after the blend."""
+        (x,) = self._in(data)
+        if self.ad.ndim(x) != 4:
+            raise ValueError("bilinear_resize: data must be 4-D")
+        N, C, Hin, Win = self.ad.shape(x)
+        m = None
+        if sub is not None:
+            (m,) = self._in(sub)
+            if self.ad.shape(m) != (N, C):
+                raise ValueError("bilinear_resize: sub must have shape %s, got %s" % ((N, C), self.ad.shape(m)))
+        if flow_rescale and C != 2:
+            raise ValueError("bilinear_resize: flow_rescale needs a (N,2,H,W) flow, got C=%d" % C)
+        out = self._out(out, x, (N, C, int(height), int(width)), "bilinear_resize")
+        self.check(self.ns.bilinear_resize_fwd(self.ad.ptr(x), self.ad.ptr(m) if m is not None else None, self.ad.ptr(out), N, C,
+                                               Hin, Win, int(height), int(width), int(bool(flow_rescale)), self.ad.stream(x)))
+        return out
+
+    def pair_mean(self, img1, img2, out=None):
+        """rgb_mean of PipelineFlownet.centralize (pipeline.py:86): (N,C) joint mean of the pair, fixed summation order."""
+        a, b = self._in(img1, img2)
+        if self.ad.ndim(a) != 4 or self.ad.shape(a) != self.ad.shape(b):
+            raise ValueError("pair_mean: img1 and img2 must be 4-D with identical shapes, got %s and %s"
+                             % (self.ad.shape(a), self.ad.shape(b)))
+        N, C, H, W = self.ad.shape(a)
+        out = self._out(out, a, (N, C), "pair_mean")
+        ws = self._workspace(a, self.ns.pair_mean_workspace_bytes(N, C, H, W))
+        self.check(self.ns.pair_mean(self.ad.ptr(a), self.ad.ptr(b), self.ad.ptr(out), N, C, H, W, self.ad.ptr(ws),
+                                     self.ad.nbytes(ws), self.ad.stream(a)))
+        return out
+
+    def preprocess_pair(self, img1, img2, height, width, mean=None, out=None):
+        """centralize + BilinearResize2D of both images in one launch (pipeline.py:120-130): -> (2N,C,height,width) with image 1
+        in rows [0,N) and image 2 in rows [N,2N), the network's input batch.  mean: (N,C), default pair_mean(img1, img2)."""
+        a, b = self._in(img1, img2)
+        if self.ad.ndim(a) != 4 or self.ad.shape(a) != self.ad.shape(b):
+            raise ValueError("preprocess_pair: img1 and img2 must be 4-D with identical shapes, got %s and %s"
+                             % (self.ad.shape(a), self.ad.shape(b)))
+        N, C, H, W = self.ad.shape(a)
+        if mean is None:
+            mean = self.pair_mean(a, b)
+        (m,) = self._in(mean)
+        if self.ad.shape(m) != (N, C):
+            raise ValueError("preprocess_pair: mean must have shape %s, got %s" % ((N, C), self.ad.shape(m)))
+        out = self._out(out, a, (2 * N, C, int(height), int(width)), "preprocess_pair")
+        self.check(self.ns.preprocess_pair(self.ad.ptr(a), self.ad.ptr(b), self.ad.ptr(m), self.ad.ptr(out), N, C, H, W,
+                                           int(height), int(width), self.ad.stream(a)))
+        return out
+
+    def flow_metric_sums(self, flow, label, mask, out=None):
+        """(N,3) per-sample sums of mfn_flow_metrics: sum mask * sqrt(|flow-label|^2 + 1e-8), sum mask, sum mask * outlier."""
+        f, l, m = self._in(flow, label, mask)
+        if self.ad.ndim(f) != 4 or self.ad.shape(f)[1] != 2 or self.ad.shape(l) != self.ad.shape(f):
+            raise ValueError("flow_metrics: flow and label must both be (N,2,H,W), got %s and %s" % (self.ad.shape(f), self.ad.shape(l)))
+        N, _, H, W = self.ad.shape(f)
+        if self.ad.shape(m) != (N, 1, H, W):
+            raise ValueError("flow_metrics: mask must have shape %s, got %s" % ((N, 1, H, W), self.ad.shape(m)))
+        out = self._out(out, f, (N, 3), "flow_metrics")
+        ws = self._workspace(f, self.ns.flow_metrics_workspace_bytes(N, H, W))
+        self.check(self.ns.flow_metrics(self.ad.ptr(f), self.ad.ptr(l), self.ad.ptr(m), self.ad.ptr(out), N, H, W, self.ad.ptr(ws),
+                                        self.ad.nbytes(ws), self.ad.stream(f)))
+        return out
+
+    def flow_metrics(self, flow, label, mask):
+        """-> (epe, fl), each (N,): EpeLossWithMask (MaskFlownet.py:576-583) and the KITTI outlier ratio (pipeline.py:182); flow and
+        label in network order (channel 0 = dy).  A sample whose mask is all zero gives nan, as the reference's 0 / 0 does."""
+        s = self.flow_metric_sums(flow, label, mask)
+        return s[:, 0] / s[:, 1], s[:, 2] / s[:, 1]
+
     def Upsample_backward(self, out_grad, factor, req="write", out=None):
         """Adjoint of Upsample(factor): (N,C,H*f,W*f) -> (N,C,H,W) (mfn_upsample_bwd)."""
         (go,) = self._in(out_grad)
@@ -819,6 +891,26 @@ def deformable_convolution_shared_backward(*a, **k):
 
 def Upsample(*a, **k):
     return default_ops().Upsample(*a, **k)
+
+
+def bilinear_resize(*a, **k):
+    return default_ops().bilinear_resize(*a, **k)
+
+
+def pair_mean(*a, **k):
+    return default_ops().pair_mean(*a, **k)
+
+
+def preprocess_pair(*a, **k):
+    return default_ops().preprocess_pair(*a, **k)
+
+
+def flow_metric_sums(*a, **k):
+    return default_ops().flow_metric_sums(*a, **k)
+
+
+def flow_metrics(*a, **k):
+    return default_ops().flow_metrics(*a, **k)
 
 
 def Convolution(*a, **k):
