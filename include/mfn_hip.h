@@ -321,7 +321,8 @@ int mfn_flow_metrics(const float *flow, const float *label, const float *mask, f
  * current shape / tuning is refused, never silently used).  3x3 / stride 1 / pad 1 layers with >= 32 filters on large images are
  * packed for the deformable convolution's matrix-core kernel (kernels/deform_conv_mma.h, CONV form): a call with such a buffer needs
  * x and out 16-byte aligned and batch strides that are multiples of 4 elements (MFN_E_ALIGN otherwise; a call that gives `w` picks
- * the other kernel by itself).
+ * the other kernel by itself).  mfn_conv2d_workspace_bytes takes no adj: for a transposed call its answer suffices for every adj
+ * the call accepts (adj_h < sh, adj_w < sw; the kernel family depends on adj).
  * ------------------------------------------------------------------------------------------- */
 int mfn_conv2d_out_shape(int H, int W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int transposed,
                          int adj_h, int adj_w, int *Ho, int *Wo);

@@ -1499,7 +1499,18 @@ static size_t conv_ws_bytes(const Settings &st, int N, int Cin, int H, int W, in
 }
 size_t MFN_API(conv2d_workspace_bytes)(int N, int Cin, int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph, int pw,
                                        int dh, int dw, int groups, int transposed) {
-  return conv_ws_bytes(settings_now(), N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, transposed);
+  const Settings st = settings_now();
+  size_t need = conv_ws_bytes(st, N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, transposed);
+  // the query has no adj, the call does, and the kernel family depends on it: room for every adj the call accepts
+  int Ho, Wo;
+  if (!transposed || conv_dims("conv2d", N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, transposed, 0, 0, &Ho, &Wo)) return need;
+  for (int ah = 0; ah < sh; ++ah)
+    for (int aw = 0; aw < sw; ++aw) {
+      if (!ah && !aw) continue;
+      const size_t b = conv_ws_bytes(st, N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, transposed, ah, aw);
+      need = need > b ? need : b;
+    }
+  return need;
 }
 
 int MFN_API(conv2d_pack_weights)(const float *w, int N, int Cin, int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph,

@@ -730,6 +730,8 @@ def test_deconv4x4_mfma(ops, oracle, pt):
     pc.case_deconv(ops, oracle, ident, ident, 1, 4, 10, 6, 9, bias=False)       # ragged tiles, filters not a multiple of 8
     emu_ops.set_tuning(conv_pt=0)
     pc.case_deconv(ops, oracle, ident, ident, 1, 4, 6, 4, 5, kernel=(3, 3), stride=(2, 2), pad=(1, 1), adj=(1, 1))   # generic kernel
+    # the same geometry on the packing kernels: the workspace query (which takes no adj) answers for every adj the call accepts
+    pc.case_deconv(ops, oracle, ident, ident, 1, 16, 8, 6, 8, kernel=(3, 3), stride=(2, 2), pad=(1, 1), adj=(1, 1), seed=1)
 
 
 def test_conv_writes_into_a_concat_slice_and_takes_packed_weights(ops, oracle):

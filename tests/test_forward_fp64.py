@@ -12,7 +12,8 @@ CPU half: the real kernel sources on the emulation (tests/emu) at small shapes t
 pyramids (CFG2: 384x512 at batch 8, CFG3: 448x1024 at batch 4).  MFN_FWD_FP64_REPORT=<file> appends the maxima per case and
 arithmetic to <file>.
 
-Kernels the forward calls cannot reach, so no case names them: conv_s2d (a stage of the strided convolutions' BACKWARD only)."""
+Kernels the forward calls cannot reach, so no case names them: conv_s2d and conv_s2d_weights (stages of the transposed convolution's
+BACKWARD only: the S2d cases of tests/test_backward_fp64.py)."""
 import os
 
 import numpy as np
@@ -235,7 +236,7 @@ def _torch_conv(x, w, b, dtype, transposed, kw):
     t = lambda a: None if a is None else torch.tensor(a, dtype=dtype)
     stride, pad, dil = kw.get("stride", (1, 1)), kw.get("pad", (1, 1) if transposed else (0, 0)), kw.get("dilate", (1, 1))
     if transposed:
-        return F.conv_transpose2d(t(x), t(w), t(b), stride=stride, padding=pad, dilation=dil).numpy()
+        return F.conv_transpose2d(t(x), t(w), t(b), stride=stride, padding=pad, output_padding=kw.get("adj", (0, 0)), dilation=dil).numpy()
     return F.conv2d(t(x), t(w), t(b), stride=stride, padding=pad, dilation=dil).numpy()
 
 
@@ -408,6 +409,9 @@ EMU_CONV = [
     (2, 37, 1, 6, 16, P1, False, None, ["conv3x3_few"], ["conv3x3_few"]),                                              # the one-filter head
     (2, 9, 16, 5, 8, {}, True, None, ["deconv_as_conv3x3_mfma"], ["deconv_as_conv3x3_bf16x3"]),                       # 4x4 / stride 2 / pad 1
     (1, 4, 10, 6, 9, dict(pad=(0, 0)), True, None, ["deconv4x4_mfma"], ["deconv4x4_mfma"]),                           # 4x4 / stride 2, another padding
+    # 3x3 / stride 2 / pad 1 / adj (1, 1), the strided layers' data gradient as a forward call: a packing kernel only with this adj, and the
+    # workspace query takes none
+    (1, 16, 8, 6, 8, dict(kernel=(3, 3), pad=(1, 1), adj=(1, 1)), True, None, ["deconv_as_conv3x3_mfma"], ["deconv_as_conv3x3_bf16x3"]),
 ]
 
 
