@@ -100,7 +100,9 @@ int mfn_correlation_fwd_into(const float *data1, const float *data2, float *out,
                              int stride2, int pad_size, int is_multiply, int activation, void *workspace,
                              size_t workspace_bytes, void *stream);
 /* Backward of the same call site (training, /root/reference/network/pipeline.py:112-113).
- * g1/g2: (N,C,H,W); req1/req2 in {MFN_REQ_NULL, MFN_REQ_WRITE, MFN_REQ_ADD}. */
+ * g1/g2: (N,C,H,W); req1/req2 in {MFN_REQ_NULL, MFN_REQ_WRITE, MFN_REQ_ADD}.  The reference configuration's kernels add in a
+ * fixed order (bit-identical from run to run); any other valid configuration runs a scatter kernel that accumulates with fp32
+ * atomics: the same results up to summation order. */
 int mfn_correlation_bwd(const float *gout, const float *data1, const float *data2, float *g1,
                         float *g2, int N, int C, int H, int W, int max_displacement,
                         int kernel_size, int stride1, int stride2, int pad_size, int is_multiply,
@@ -118,7 +120,8 @@ int mfn_correlation_bwd(const float *gout, const float *data1, const float *data
 int mfn_warp_fwd(const float *x, const float *flow_yx, float *out, int N, int C, int H, int W,
                  int clip_grid, void *stream);
 /* gx: (N,C,H,W) data gradient, gflow_yx: (N,2,H,W) flow gradient (NULL / MFN_REQ_NULL to skip,
- * which is what block_grad=True in layer.py:15-16 does). */
+ * which is what block_grad=True in layer.py:15-16 does).  gx is scattered with fp32 atomics (as MXNet's GPU kernel does): its
+ * bit-level results can differ from run to run by summation order; gflow_yx is deterministic. */
 int mfn_warp_bwd(const float *gout, const float *x, const float *flow_yx, float *gx,
                  float *gflow_yx, int N, int C, int H, int W, int clip_grid, int req_x,
                  int req_flow, void *stream);
@@ -130,7 +133,8 @@ int mfn_bilinear_sampler_fwd(const float *data, const float *grid, float *out, i
                              int iH, int iW, int oH, int oW, void *stream);
 /* Backward of the operator pair (what MXNet's autograd reaches where the reference differentiates a warp it built
  * from the two operators: c40 of /root/reference/network/MaskFlownet.py:311, block_grad=False).  gdata: (N,C,iH,iW),
- * ggrid: (N,2,oH,oW) channel 0 = x; gflow_xy = ggrid / ((size-1)/2).  req in {MFN_REQ_NULL, _WRITE, _ADD}. */
+ * ggrid: (N,2,oH,oW) channel 0 = x; gflow_xy = ggrid / ((size-1)/2).  req in {MFN_REQ_NULL, _WRITE, _ADD}.  gdata is scattered
+ * with fp32 atomics: the same results up to summation order from run to run; ggrid is deterministic. */
 int mfn_bilinear_sampler_bwd(const float *gout, const float *data, const float *grid, float *gdata,
                              float *ggrid, int N, int C, int iH, int iW, int oH, int oW,
                              int req_data, int req_grid, void *stream);

@@ -384,7 +384,11 @@ def test_emu_deform_flow_and_matching(emu, _emu_defaults, arith, kind):
         case_deform_flow(emu, arith, 1, 32, 6, 8, kind, EMU_DC_KERNEL[arith], bias="small")
 
 
-@pytest.mark.parametrize("mt,pt,nw,C", [(1, 4, 4, 32), (2, 3, 12, 64), (2, 2, 4, 64), (3, 1, 6, 96), (1, 1, 8, 128), (1, 1, 4, 64), (1, 1, 2, 32), (1, 1, 1, 48)])
+# dc_mma_kernel's tilings (filter tiles per wave, pixel tiles per block, waves per block) and a channel count they divide
+EMU_DCM_TILINGS = [(1, 4, 4, 32), (2, 3, 12, 64), (2, 2, 4, 64), (3, 1, 6, 96), (1, 1, 8, 128), (1, 1, 4, 64), (1, 1, 2, 32), (1, 1, 1, 48)]
+
+
+@pytest.mark.parametrize("mt,pt,nw,C", EMU_DCM_TILINGS)
 def test_emu_deform_matrix_core_tilings(emu, _emu_defaults, mt, pt, nw, C):
     """Every tiling of tests/test_emu_parity.py DCM_TILINGS once, graded-pixel input."""
     case_deform(emu, -1, 1, C, 6, 8, "smooth", "graded-pixel", "dc_mma", tuning=dict(dc_mt=mt, dc_pt=pt, dc_nw=nw))

@@ -1,0 +1,373 @@
+// emu_bounds -- the kernel sources on the CPU emulation (tests/emu/emu_api.cpp) under AddressSanitizer / UBSan, called through the
+// mfn_emu_* entries with every buffer a heap block of exactly its tensor or queried size.  A stand-alone program: nothing is loaded into
+// Python, nothing is preloaded, no GPU is involved.  tests/test_memory_contract.py sees writes next to a buffer and reads that reach a
+// result; here the sanitizer sees every access outside a block at any distance, discarded over-reads and the emulated LDS included.
+// The list is one call per kernel family and route of that test, driven by the tables below; built and run by tools/emu_bounds.py.
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#define mfn_last_error mfn_emu_last_error
+#define mfn_set_tuning mfn_emu_set_tuning
+#define mfn_set_arithmetic mfn_emu_set_arithmetic
+#define mfn_correlation_out_shape mfn_emu_correlation_out_shape
+#define mfn_correlation_workspace_bytes mfn_emu_correlation_workspace_bytes
+#define mfn_correlation_fwd_into mfn_emu_correlation_fwd_into
+#define mfn_correlation_bwd mfn_emu_correlation_bwd
+#define mfn_warp_fwd mfn_emu_warp_fwd
+#define mfn_warp_bwd mfn_emu_warp_bwd
+#define mfn_grid_generator_warp mfn_emu_grid_generator_warp
+#define mfn_grid_generator_affine mfn_emu_grid_generator_affine
+#define mfn_bilinear_sampler_fwd mfn_emu_bilinear_sampler_fwd
+#define mfn_bilinear_sampler_bwd mfn_emu_bilinear_sampler_bwd
+#define mfn_grid_generator_warp_bwd mfn_emu_grid_generator_warp_bwd
+#define mfn_deform_conv_workspace_bytes mfn_emu_deform_conv_workspace_bytes
+#define mfn_deform_conv_fwd mfn_emu_deform_conv_fwd
+#define mfn_deform_conv_shared_fwd mfn_emu_deform_conv_shared_fwd
+#define mfn_deform_conv_packed_weight_bytes mfn_emu_deform_conv_packed_weight_bytes
+#define mfn_deform_conv_pack_weights mfn_emu_deform_conv_pack_weights
+#define mfn_deform_conv_fwd_packed mfn_emu_deform_conv_fwd_packed
+#define mfn_deform_conv_matching_fwd mfn_emu_deform_conv_matching_fwd
+#define mfn_deform_conv_bwd_workspace_bytes mfn_emu_deform_conv_bwd_workspace_bytes
+#define mfn_deform_conv_bwd mfn_emu_deform_conv_bwd
+#define mfn_deform_conv_shared_bwd_workspace_bytes mfn_emu_deform_conv_shared_bwd_workspace_bytes
+#define mfn_deform_conv_shared_bwd mfn_emu_deform_conv_shared_bwd
+#define mfn_offsets_from_flow_bwd mfn_emu_offsets_from_flow_bwd
+#define mfn_upsample_fwd mfn_emu_upsample_fwd
+#define mfn_upsample_bwd mfn_emu_upsample_bwd
+#define mfn_leaky_relu_bwd mfn_emu_leaky_relu_bwd
+#define mfn_offsets_from_flow mfn_emu_offsets_from_flow
+#define mfn_pair_mean_workspace_bytes mfn_emu_pair_mean_workspace_bytes
+#define mfn_pair_mean mfn_emu_pair_mean
+#define mfn_preprocess_pair mfn_emu_preprocess_pair
+#define mfn_bilinear_resize_fwd mfn_emu_bilinear_resize_fwd
+#define mfn_flow_metrics_workspace_bytes mfn_emu_flow_metrics_workspace_bytes
+#define mfn_flow_metrics mfn_emu_flow_metrics
+#define mfn_conv2d_out_shape mfn_emu_conv2d_out_shape
+#define mfn_conv2d_workspace_bytes mfn_emu_conv2d_workspace_bytes
+#define mfn_conv2d_packed_weight_bytes mfn_emu_conv2d_packed_weight_bytes
+#define mfn_conv2d_pack_weights mfn_emu_conv2d_pack_weights
+#define mfn_conv2d_fwd mfn_emu_conv2d_fwd
+#define mfn_conv2d_bwd_workspace_bytes mfn_emu_conv2d_bwd_workspace_bytes
+#define mfn_conv2d_bwd mfn_emu_conv2d_bwd
+#include "../../include/mfn_hip.h"
+extern "C" int mfn_emu_test_launch_log(char *buf, int cap);
+
+// A heap block of exactly `bytes` bytes, 64-byte aligned (the alignment the plans ask about), freed at the end of the call's scope.
+struct Block {
+  void *p = nullptr;
+  size_t bytes = 0;
+  explicit Block(size_t b) : bytes(b) {
+    if (b && posix_memalign(&p, 64, b)) abort();
+  }
+  Block(const Block &) = delete;
+  ~Block() { free(p); }
+  float *f() const { return (float *)p; }
+};
+static unsigned g_seed = 12345u;
+static float rnd() {   // uniform in [-1, 1)
+  g_seed = g_seed * 1664525u + 1013904223u;
+  return (float)(g_seed >> 8) * (2.0f / 16777216.0f) - 1.0f;
+}
+struct Tensor : Block {
+  size_t n;
+  explicit Tensor(size_t count, float scale = 1.f, bool fill = true) : Block(count * sizeof(float)), n(count) {
+    for (size_t i = 0; fill && i < n; ++i) f()[i] = rnd() * scale;
+  }
+};
+
+struct KV { const char *key; int value; };
+static int g_failed = 0, g_calls = 0;
+static std::vector<std::string> g_touched;
+static void tune(const std::vector<KV> &kv) {
+  for (const KV &t : kv) {
+    int rc;
+    if (!strcmp(t.key, "correlation") || !strcmp(t.key, "deformable_convolution") || !strcmp(t.key, "convolution")) rc = mfn_set_arithmetic(t.key, t.value);
+    else rc = mfn_set_tuning(t.key, t.value);
+    if (rc) { printf("  setting %s=%d refused: %s\n", t.key, t.value, mfn_last_error()); ++g_failed; }
+    g_touched.push_back(t.key);
+  }
+}
+static void untune() {
+  for (const std::string &k : g_touched) {
+    if (k == "correlation" || k == "deformable_convolution" || k == "convolution") mfn_set_arithmetic(k.c_str(), -1);
+    else mfn_set_tuning(k.c_str(), k == "corr.variant" ? -1 : 0);
+  }
+  g_touched.clear();
+}
+static void report(const char *what, int rc) {
+  char log[4096];
+  mfn_emu_test_launch_log(log, sizeof(log));
+  ++g_calls;
+  if (rc) { ++g_failed; printf("%-44s status %d: %s\n", what, rc, mfn_last_error()); }
+  else printf("%-44s ok   %s\n", what, log);
+  fflush(stdout);
+  untune();
+}
+
+// ---- correlation ------------------------------------------------------------------------------------------------------------------------
+struct CorrRow { const char *name; std::vector<KV> t; int N, C, H, W, md, k, s1, pad, c0; };
+static void corr_fwd(const CorrRow &r) {
+  tune(r.t);
+  int tc, th, tw;
+  if (mfn_correlation_out_shape(r.H, r.W, r.md, r.k, r.s1, 1, r.pad, &tc, &th, &tw)) return report(r.name, -1);
+  const size_t in = (size_t)r.N * r.C * r.H * r.W, img = (size_t)th * tw, extra = r.c0 ? 7 : 0;
+  Tensor d1(in), d2(in), out((size_t)r.N * (r.c0 + tc + extra) * img, 1.f, false);
+  const size_t need = mfn_correlation_workspace_bytes(r.N, r.C, r.H, r.W, r.md, r.k, r.s1, 1, r.pad, 1);
+  Block ws(need);
+  report(r.name, mfn_correlation_fwd_into(d1.f(), d2.f(), out.f() + r.c0 * img, r.c0 ? (long long)((r.c0 + tc + extra) * img) : 0, r.N, r.C, r.H,
+                                          r.W, r.md, r.k, r.s1, 1, r.pad, 1, MFN_ACT_LEAKY_0_1, ws.p, need, nullptr));
+}
+struct CorrBwdRow { const char *name; std::vector<KV> t; int N, C, H, W, md, k, s1, pad, req1, req2; };
+static void corr_bwd(const CorrBwdRow &r) {
+  tune(r.t);
+  int tc, th, tw;
+  if (mfn_correlation_out_shape(r.H, r.W, r.md, r.k, r.s1, 1, r.pad, &tc, &th, &tw)) return report(r.name, -1);
+  const size_t in = (size_t)r.N * r.C * r.H * r.W;
+  Tensor go((size_t)r.N * tc * th * tw), d1(in), d2(in), g1(r.req1 ? in : 0), g2(r.req2 ? in : 0);
+  report(r.name, mfn_correlation_bwd(go.f(), d1.f(), d2.f(), g1.f(), g2.f(), r.N, r.C, r.H, r.W, r.md, r.k, r.s1, 1, r.pad, 1, r.req1, r.req2, nullptr));
+}
+
+// ---- deformable convolution -------------------------------------------------------------------------------------------------------------
+enum { DROPIN, PACKED, SHARED, MATCHING };
+struct DcRow { const char *name; std::vector<KV> t; int N, Cin, Cout, H, W, groups, dg, entry; };
+static void dc_fwd(const DcRow &r) {
+  tune(r.t);
+  const size_t px = (size_t)r.H * r.W;
+  Tensor x((size_t)r.N * r.Cin * px), off((size_t)r.N * 18 * r.dg * px, 1.5f), fl((size_t)r.N * 2 * px, 0.6f), w((size_t)r.Cout * (r.Cin / r.groups) * 9, 0.1f),
+      b(r.Cout), mask((size_t)r.N * px), tr((size_t)r.N * r.Cout * px), out((size_t)r.N * r.Cout * px, 1.f, false);
+  const size_t need = mfn_deform_conv_workspace_bytes(r.N, r.Cin, r.H, r.W, r.Cout, 3, 3, 1, 1, 1, 1, 1, 1, r.groups, r.dg);
+  Block ws(need);
+  int rc;
+  if (r.entry == PACKED) {
+    const size_t pb = mfn_deform_conv_packed_weight_bytes(r.N, r.Cin, r.H, r.W, r.Cout, 3, 3, 1, 1, 1, 1, 1, 1, r.groups, r.dg);
+    Block packed(pb);
+    unsigned long long tag = 0;
+    rc = mfn_deform_conv_pack_weights(w.f(), r.N, r.Cin, r.H, r.W, r.Cout, 3, 3, 1, 1, 1, 1, 1, 1, r.groups, r.dg, packed.p, pb, &tag, nullptr);
+    if (!rc) rc = mfn_deform_conv_fwd_packed(x.f(), off.f(), packed.p, pb, tag, b.f(), out.f(), r.N, r.Cin, r.H, r.W, r.Cout, 3, 3, 1, 1, 1, 1, 1, 1, r.groups,
+                                             r.dg, ws.p, need, nullptr);
+  } else if (r.entry == SHARED) {
+    rc = mfn_deform_conv_shared_fwd(x.f(), fl.f(), 20.f, 8.f, w.f(), b.f(), out.f(), r.N, r.Cin, r.H, r.W, r.Cout, 3, 3, 1, 1, 1, 1, r.groups, ws.p, need, nullptr);
+  } else if (r.entry == MATCHING) {
+    rc = mfn_deform_conv_matching_fwd(x.f(), fl.f(), 20.f, 8.f, w.f(), nullptr, 0, 0, b.f(), mask.f(), tr.f(), 1, out.f(), r.N, r.Cin, r.H, r.W, r.Cout, 3, 3, 1,
+                                      1, 1, 1, r.groups, ws.p, need, nullptr);
+  } else {
+    rc = mfn_deform_conv_fwd(x.f(), off.f(), w.f(), b.f(), out.f(), r.N, r.Cin, r.H, r.W, r.Cout, 3, 3, 1, 1, 1, 1, 1, 1, r.groups, r.dg, ws.p, need, nullptr);
+  }
+  report(r.name, rc);
+}
+struct DcBwdRow { const char *name; std::vector<KV> t; int N, Cin, Cout, H, W, flow, no_ws, req[4]; };
+static void dc_bwd(const DcBwdRow &r) {
+  tune(r.t);
+  const size_t px = (size_t)r.H * r.W, nx = (size_t)r.N * r.Cin * px, nw = (size_t)r.Cout * r.Cin * 9, no = (size_t)r.N * (r.flow ? 2 : 18) * px;
+  Tensor go((size_t)r.N * r.Cout * px), x(nx), off(no, r.flow ? 0.6f : 1.5f), w(nw, 0.1f);
+  Tensor gx(r.req[0] ? nx : 0), goff(r.req[1] ? no : 0), gw(r.req[2] ? nw : 0), gb(r.req[3] ? r.Cout : 0);
+  size_t need = r.flow ? mfn_deform_conv_shared_bwd_workspace_bytes(r.N, r.Cin, r.H, r.W, r.Cout, 3, 3, 1, 1, 1, 1, 1)
+                       : mfn_deform_conv_bwd_workspace_bytes(r.N, r.Cin, r.H, r.W, r.Cout, 3, 3, 1, 1, 1, 1, 1, 1, 1, 1);
+  if (r.no_ws) need = 0;
+  Block ws(need);
+  int rc;
+  if (r.flow)
+    rc = mfn_deform_conv_shared_bwd(go.f(), x.f(), off.f(), 20.f, 8.f, w.f(), gx.f(), goff.f(), gw.f(), gb.f(), r.N, r.Cin, r.H, r.W, r.Cout, 3, 3, 1, 1, 1, 1, 1,
+                                    r.req[0], r.req[1], r.req[2], r.req[3], ws.p, need, nullptr);
+  else
+    rc = mfn_deform_conv_bwd(go.f(), x.f(), off.f(), w.f(), gx.f(), goff.f(), gw.f(), gb.f(), r.N, r.Cin, r.H, r.W, r.Cout, 3, 3, 1, 1, 1, 1, 1, 1, 1, 1, r.req[0],
+                             r.req[1], r.req[2], r.req[3], ws.p, need, nullptr);
+  report(r.name, rc);
+}
+
+// ---- convolution / deconvolution ----------------------------------------------------------------------------------------------------------
+struct ConvRow { const char *name; std::vector<KV> t; int N, Cin, Cout, H, W, k, s, p, d, tr, adj, packed, act, bwd, req[3]; };
+static void conv(const ConvRow &r) {
+  tune(r.t);
+  int Ho, Wo;
+  if (mfn_conv2d_out_shape(r.H, r.W, r.k, r.k, r.s, r.s, r.p, r.p, r.d, r.d, r.tr, r.adj, r.adj, &Ho, &Wo)) return report(r.name, -1);
+  const size_t nx = (size_t)r.N * r.Cin * r.H * r.W, nw = (size_t)r.Cin * r.Cout * r.k * r.k, ny = (size_t)r.N * r.Cout * Ho * Wo;
+  Tensor x(nx), w(nw, 0.1f), b(r.Cout), y(ny, 1.f, false);
+  int rc;
+  {
+    size_t need = mfn_conv2d_workspace_bytes(r.N, r.Cin, r.H, r.W, r.Cout, r.k, r.k, r.s, r.s, r.p, r.p, r.d, r.d, 1, r.tr);
+    if (r.packed) {
+      const size_t pb = mfn_conv2d_packed_weight_bytes(r.N, r.Cin, r.H, r.W, r.Cout, r.k, r.k, r.s, r.s, r.p, r.p, r.d, r.d, 1, r.tr);
+      Block packed(pb);
+      unsigned long long tag = 0;
+      rc = mfn_conv2d_pack_weights(w.f(), r.N, r.Cin, r.H, r.W, r.Cout, r.k, r.k, r.s, r.s, r.p, r.p, r.d, r.d, 1, r.tr, packed.p, pb, &tag, nullptr);
+      if (tag != 0x4d43ffff00000000ull) need = 0;   // packed for a matrix-core plan: no re-layout scratch
+      Block ws(need);
+      if (!rc) rc = mfn_conv2d_fwd(x.f(), 0, nullptr, packed.p, pb, tag, b.f(), y.f(), 0, r.N, r.Cin, r.H, r.W, r.Cout, r.k, r.k, r.s, r.s, r.p, r.p, r.d, r.d, 1,
+                                   r.tr, r.adj, r.adj, r.act, ws.p, need, nullptr);
+    } else {
+      Block ws(need);
+      rc = mfn_conv2d_fwd(x.f(), 0, w.f(), nullptr, 0, 0, b.f(), y.f(), 0, r.N, r.Cin, r.H, r.W, r.Cout, r.k, r.k, r.s, r.s, r.p, r.p, r.d, r.d, 1, r.tr, r.adj, r.adj,
+                          r.act, ws.p, need, nullptr);
+    }
+  }
+  if (!rc && r.bwd) {
+    Tensor go(ny), gx(r.req[0] ? nx : 0), gw(r.req[1] ? nw : 0), gb(r.req[2] ? r.Cout : 0);
+    const size_t need = mfn_conv2d_bwd_workspace_bytes(r.N, r.Cin, r.H, r.W, r.Cout, r.k, r.k, r.s, r.s, r.p, r.p, r.d, r.d, 1, r.tr, r.adj, r.adj, r.act);
+    Block ws(need);
+    rc = mfn_conv2d_bwd(go.f(), x.f(), w.f(), r.act ? y.f() : nullptr, gx.f(), gw.f(), gb.f(), r.N, r.Cin, r.H, r.W, r.Cout, r.k, r.k, r.s, r.s, r.p, r.p, r.d, r.d, 1,
+                        r.tr, r.adj, r.adj, r.act, r.req[0], r.req[1], r.req[2], ws.p, need, nullptr);
+  }
+  report(r.name, rc);
+}
+
+// ---- entries without a workspace, and the predict entries ---------------------------------------------------------------------------------
+static void others() {
+  {
+    const int N = 2, C = 3, H = 8, W = 11;
+    const size_t n = (size_t)N * C * H * W, nf = (size_t)N * 2 * H * W;
+    for (int clip = 0; clip < 2; ++clip) {
+      Tensor x(n), fl(nf, 3.f), out(n, 1.f, false), go(n), gx(n, 1.f, false), gf(nf, 1.f, false);
+      report(clip ? "warp_fwd clip" : "warp_fwd", mfn_warp_fwd(x.f(), fl.f(), out.f(), N, C, H, W, clip, nullptr));
+      report(clip ? "warp_bwd clip" : "warp_bwd", mfn_warp_bwd(go.f(), x.f(), fl.f(), gx.f(), gf.f(), N, C, H, W, clip, 1, 1, nullptr));
+    }
+  }
+  {
+    Tensor fl(2 * 2 * 6 * 9, 2.f), grid(2 * 2 * 6 * 9, 1.f, false), theta(2 * 6), ga(2 * 2 * 5 * 7, 1.f, false), gflow(2 * 2 * 6 * 9, 1.f, false);
+    report("grid_generator_warp", mfn_grid_generator_warp(fl.f(), grid.f(), 2, 6, 9, nullptr));
+    report("grid_generator_affine", mfn_grid_generator_affine(theta.f(), ga.f(), 2, 5, 7, nullptr));
+    report("grid_generator_warp_bwd", mfn_grid_generator_warp_bwd(fl.f(), gflow.f(), 2, 6, 9, 1, nullptr));
+    Tensor d(1 * 2 * 6 * 9), g(1 * 2 * 5 * 7, 1.2f), out(1 * 2 * 5 * 7, 1.f, false), go(1 * 2 * 5 * 7), gd(1 * 2 * 6 * 9, 1.f, false), gg(1 * 2 * 5 * 7, 1.f, false);
+    report("bilinear_sampler_fwd", mfn_bilinear_sampler_fwd(d.f(), g.f(), out.f(), 1, 2, 6, 9, 5, 7, nullptr));
+    report("bilinear_sampler_bwd", mfn_bilinear_sampler_bwd(go.f(), d.f(), g.f(), gd.f(), gg.f(), 1, 2, 6, 9, 5, 7, 1, 1, nullptr));
+  }
+  for (int f : {1, 2, 8, 16}) {
+    const int H = 5, W = 7;
+    Tensor x(2 * H * W), out((size_t)2 * H * f * W * f, 1.f, false), gx(2 * H * W, 1.f, false);
+    char name[64];
+    snprintf(name, sizeof(name), "upsample_fwd x%d", f);
+    report(name, mfn_upsample_fwd(x.f(), out.f(), 1, 2, H, W, f, nullptr));
+    Tensor go((size_t)2 * H * f * W * f);
+    snprintf(name, sizeof(name), "upsample_bwd x%d", f);
+    report(name, mfn_upsample_bwd(go.f(), gx.f(), 1, 2, H, W, f, 1, nullptr));
+  }
+  for (size_t n : {(size_t)1, (size_t)3, (size_t)4, (size_t)1023, (size_t)1025}) {
+    Tensor go(n), y(n), gi(n, 1.f, false);
+    char name[64];
+    snprintf(name, sizeof(name), "leaky_relu_bwd n=%zu", n);
+    report(name, mfn_leaky_relu_bwd(go.f(), y.f(), gi.f(), n, 0.1f, nullptr));
+  }
+  for (int W : {6, 8}) {
+    Tensor fl(2 * 2 * 5 * W), off(2 * 18 * 5 * W, 1.f, false), goff(2 * 18 * 5 * W), gfl(2 * 2 * 5 * W, 1.f, false);
+    report(W == 6 ? "offsets_from_flow W=6" : "offsets_from_flow W=8", mfn_offsets_from_flow(fl.f(), off.f(), 2, 5, W, 9, 20.f, 16.f, nullptr));
+    report(W == 6 ? "offsets_from_flow_bwd W=6" : "offsets_from_flow_bwd W=8", mfn_offsets_from_flow_bwd(goff.f(), gfl.f(), 2, 5, W, 9, 20.f, 16.f, 1, nullptr));
+  }
+  {
+    const int N = 2, C = 3, H = 9, W = 13;
+    Tensor a((size_t)N * C * H * W, 100.f), b((size_t)N * C * H * W, 100.f), mean(N * C, 1.f, false), out((size_t)2 * N * C * 6 * 10, 1.f, false);
+    const size_t need = mfn_pair_mean_workspace_bytes(N, C, H, W);
+    Block ws(need);
+    report("pair_mean", mfn_pair_mean(a.f(), b.f(), mean.f(), N, C, H, W, ws.p, need, nullptr));
+    report("preprocess_pair", mfn_preprocess_pair(a.f(), b.f(), mean.f(), out.f(), N, C, H, W, 6, 10, nullptr));
+    Tensor up((size_t)N * C * 12 * 17, 1.f, false), down((size_t)N * C * 5 * 6, 1.f, false), same((size_t)N * C * H * W, 1.f, false);
+    report("bilinear_resize up, sub", mfn_bilinear_resize_fwd(a.f(), mean.f(), up.f(), N, C, H, W, 12, 17, 0, nullptr));
+    report("bilinear_resize down", mfn_bilinear_resize_fwd(a.f(), nullptr, down.f(), N, C, H, W, 5, 6, 0, nullptr));
+    report("bilinear_resize equal", mfn_bilinear_resize_fwd(a.f(), nullptr, same.f(), N, C, H, W, H, W, 0, nullptr));
+    report("bilinear_resize equal, sub", mfn_bilinear_resize_fwd(a.f(), mean.f(), same.f(), N, C, H, W, H, W, 0, nullptr));
+    Tensor fl((size_t)N * 2 * H * W, 4.f), lab((size_t)N * 2 * H * W, 4.f), mask((size_t)N * H * W), sums(N * 3, 1.f, false), flup((size_t)N * 2 * 12 * 17, 1.f, false);
+    report("bilinear_resize flow rescale", mfn_bilinear_resize_fwd(fl.f(), nullptr, flup.f(), N, 2, H, W, 12, 17, 1, nullptr));
+    const size_t need2 = mfn_flow_metrics_workspace_bytes(N, H, W);
+    Block ws2(need2);
+    report("flow_metrics", mfn_flow_metrics(fl.f(), lab.f(), mask.f(), sums.f(), N, H, W, ws2.p, need2, nullptr));
+  }
+}
+
+int main() {
+  const std::vector<KV> D2 = {{"corr.direct", 2}};
+  const std::vector<CorrRow> corr = {
+      {"corr gram v48", {{"corr.variant", 48}, {"corr.direct", 2}}, 1, 32, 10, 24, 4, 1, 1, 4, 0},
+      {"corr gram v48 rows 8, into a slice", {{"corr.variant", 48}, {"corr.direct", 2}, {"corr.rows", 8}}, 2, 32, 13, 20, 4, 1, 1, 4, 4},
+      {"corr gram v48c2", {{"corr.variant", 48}, {"corr.direct", 2}, {"corr.rows", 2}}, 1, 64, 9, 24, 4, 1, 1, 4, 0},
+      {"corr gram v46", {{"corr.variant", 46}, {"corr.direct", 2}, {"corr.rows", 6}}, 1, 32, 7, 36, 2, 1, 1, 2, 0},
+      {"corr gramk v44", {{"corr.variant", 44}, {"corr.direct", 2}}, 1, 96, 5, 16, 4, 1, 1, 4, 0},
+      {"corr gramk v45", {{"corr.variant", 45}, {"corr.direct", 2}}, 1, 64, 4, 24, 2, 1, 1, 2, 0},
+      {"corr dma v26", {{"corr.variant", 26}, {"corr.direct", 2}}, 1, 12, 6, 40, 4, 1, 1, 4, 0},
+      {"corr direct", {{"corr.direct", 1}}, 2, 30, 6, 8, 4, 1, 1, 4, 0},
+      {"corr tiled v6 + reduce", {{"corr.variant", 6}, {"corr.direct", 2}}, 2, 32, 7, 16, 4, 1, 1, 4, 0},
+      {"corr tiled v6 + reduce, into a slice", {{"corr.variant", 6}, {"corr.direct", 2}}, 2, 16, 7, 16, 4, 1, 1, 4, 4},
+      {"corr plan fp32 (1,96,5,16)", {{"correlation", 0}}, 1, 96, 5, 16, 4, 1, 1, 4, 0},
+      {"corr generic k3 s1=2", {}, 2, 3, 9, 10, 2, 3, 2, 3, 0},
+      {"corr unaligned slice", {}, 2, 5, 5, 6, 4, 1, 1, 4, 3},
+      {"corr odd width", {}, 1, 3, 5, 7, 4, 1, 1, 4, 0},
+      {"corr W=30", {}, 2, 8, 20, 30, 2, 1, 1, 2, 0},
+  };
+  for (const CorrRow &r : corr) corr_fwd(r);
+  const std::vector<CorrBwdRow> cbwd = {
+      {"corr_bwd lds ww", {}, 2, 5, 6, 16, 4, 1, 1, 4, 1, 1},
+      {"corr_bwd lds wn", {}, 2, 5, 6, 16, 4, 1, 1, 4, 1, 0},
+      {"corr_bwd block na", {{"bwd.off", 4}}, 2, 5, 6, 16, 4, 1, 1, 4, 0, 3},
+      {"corr_bwd block ww", {{"bwd.off", 4}}, 2, 5, 6, 16, 4, 1, 1, 4, 1, 1},
+      {"corr_bwd gather W=7 ww", {}, 2, 3, 5, 7, 4, 1, 1, 4, 1, 1},
+      {"corr_bwd gather W=7 na", {}, 2, 3, 5, 7, 4, 1, 1, 4, 0, 3},
+      {"corr_bwd generic ww", {}, 2, 3, 9, 10, 2, 3, 2, 3, 1, 1},
+  };
+  for (const CorrBwdRow &r : cbwd) corr_bwd(r);
+  const std::vector<DcRow> dc = {
+      {"dc_mma 1x4x4 C32", {{"dc.mt", 1}, {"dc.pt", 4}, {"dc.nw", 4}}, 1, 32, 32, 6, 8, 1, 1, DROPIN},
+      {"dc_mma 2x3x12 C64", {{"dc.mt", 2}, {"dc.pt", 3}, {"dc.nw", 12}}, 1, 64, 64, 6, 8, 1, 1, DROPIN},
+      {"dc_mma 3x1x6 C96", {{"dc.mt", 3}, {"dc.pt", 1}, {"dc.nw", 6}}, 1, 96, 96, 6, 8, 1, 1, DROPIN},
+      {"dc_mma 1x1x1 C48", {{"dc.mt", 1}, {"dc.pt", 1}, {"dc.nw", 1}}, 1, 48, 48, 6, 8, 1, 1, DROPIN},
+      {"dc_mma packed", {}, 1, 32, 32, 6, 8, 1, 1, PACKED},
+      {"dc_mma shared", {}, 1, 32, 32, 6, 8, 1, 1, SHARED},
+      {"dc_mma matching", {}, 1, 32, 32, 6, 8, 1, 1, MATCHING},
+      {"dc_lds fp32", {{"deformable_convolution", 0}}, 1, 32, 32, 8, 16, 1, 1, DROPIN},
+      {"dc_lds fp32 W=7", {{"deformable_convolution", 0}}, 1, 32, 32, 6, 7, 1, 1, SHARED},
+      {"dc_lds fp32 packed", {{"deformable_convolution", 0}}, 1, 32, 32, 6, 8, 1, 1, PACKED},
+      {"dc_lds split K", {{"deformable_convolution", 0}, {"dc.pt", 1}, {"dc.ksb", 2}}, 1, 32, 32, 4, 8, 1, 1, DROPIN},
+      {"dc_lds split K matching", {{"deformable_convolution", 0}, {"dc.pt", 1}, {"dc.ksb", 2}}, 1, 32, 32, 4, 8, 1, 1, MATCHING},
+      {"dc generic groups 2", {}, 2, 4, 6, 6, 7, 2, 1, DROPIN},
+      {"dc generic deformable groups 2", {}, 2, 4, 6, 6, 7, 1, 2, DROPIN},
+  };
+  for (const DcRow &r : dc) dc_fwd(r);
+  const std::vector<DcBwdRow> dcb = {
+      {"dc_bwd pix + pc slabs", {}, 1, 4, 4, 5, 16, 0, 0, {1, 1, 1, 1}},
+      {"dc_bwd pix + pc slabs add", {}, 1, 4, 4, 5, 16, 0, 0, {3, 3, 3, 3}},
+      {"dc_bwd weights only", {}, 1, 4, 4, 5, 16, 0, 0, {0, 0, 1, 0}},
+      {"dc_bwd pc atomics (no workspace)", {}, 1, 4, 4, 5, 16, 0, 1, {1, 1, 1, 1}},
+      {"dc_bwd tile + mfma W=17", {}, 1, 2, 4, 9, 17, 0, 0, {1, 1, 1, 1}},
+      {"dc_bwd generic", {{"path.generic", 2}}, 1, 4, 4, 5, 16, 0, 0, {1, 1, 1, 1}},
+      {"dc_bwd tile (bwd.off=1)", {{"bwd.off", 1}}, 1, 4, 4, 4, 16, 0, 0, {1, 1, 1, 1}},
+      {"dc_bwd 100 filters", {}, 1, 8, 100, 5, 8, 0, 0, {1, 1, 1, 1}},
+      {"dc_bwd ragged blocks (1,36,40,5,16)", {}, 1, 36, 40, 5, 16, 0, 0, {1, 1, 1, 1}},
+      // 261 tiles of 8x4 pixels: two per block of the weight kernel, one in the last (tpb = 2, nblk = 131 in dc_bwd_plan); slabs per block
+      {"dc_bwd pc slabs, two tiles per block", {}, 1, 4, 4, 116, 72, 0, 0, {0, 0, 1, 1}},
+      {"dc_shared_bwd flow mode", {}, 1, 4, 4, 5, 8, 1, 0, {1, 1, 1, 1}},
+      {"dc_shared_bwd composed", {{"bwd.off", 2}}, 1, 4, 4, 5, 8, 1, 0, {1, 3, 1, 1}},
+      {"dc_shared_bwd composed W=17", {}, 1, 2, 4, 9, 17, 1, 0, {1, 1, 1, 1}},
+  };
+  for (const DcBwdRow &r : dcb) dc_bwd(r);
+  const std::vector<KV> F32 = {{"convolution", 0}}, DCM = {{"conv.dcm", 2}}, G4 = {{"path.generic", 4}}, G2 = {{"path.generic", 2}};
+  const std::vector<ConvRow> convs = {
+      //                                      N  Cin Cout H   W  k  s  p  d tr adj packed act bwd req
+      {"conv3x3 bf16x3 + bwd", {}, 1, 8, 32, 8, 16, 3, 1, 1, 1, 0, 0, 0, 1, 1, {1, 1, 1}},
+      {"conv3x3 mfma + bwd", F32, 1, 8, 32, 8, 16, 3, 1, 1, 1, 0, 0, 0, 1, 1, {1, 1, 1}},
+      {"conv3x3 stride 2 + bwd (deconv adj11)", {}, 1, 8, 16, 12, 16, 3, 2, 1, 1, 0, 0, 0, 0, 1, {1, 1, 1}},
+      {"conv3x3 stride 2 fp32 + bwd (adj00)", F32, 1, 8, 16, 13, 17, 3, 2, 1, 1, 0, 0, 0, 0, 1, {1, 1, 1}},
+      {"conv3x3 dcm + bwd", DCM, 2, 37, 32, 6, 16, 3, 1, 1, 1, 0, 0, 0, 1, 1, {1, 1, 1}},
+      {"conv3x3 dilated + bwd (flip, wgrad)", {}, 1, 4, 8, 12, 16, 3, 1, 2, 2, 0, 0, 0, 1, 1, {1, 1, 1}},
+      {"conv3x3 dilated W=12 + bwd (flip, mfma)", F32, 1, 4, 8, 12, 12, 3, 1, 2, 2, 0, 0, 0, 1, 1, {3, 3, 3}},
+      {"conv 1x1 generic", {}, 2, 6, 8, 7, 9, 1, 1, 0, 1, 0, 0, 0, 0, 0, {0, 0, 0}},
+      {"conv3x3 few (2 filters) + bwd", {}, 2, 37, 2, 6, 16, 3, 1, 1, 1, 0, 0, 0, 0, 1, {1, 1, 1}},
+      {"conv3x3 W=12 + bwd (pc slabs)", {}, 2, 4, 6, 8, 12, 3, 1, 1, 1, 0, 0, 0, 1, 1, {1, 1, 1}},
+      {"conv3x3 65x64 + bwd (two-stage bias)", {}, 1, 4, 2, 65, 64, 3, 1, 1, 1, 0, 0, 0, 0, 1, {1, 0, 3}},
+      {"conv3x3 + bwd path.generic=4", G4, 1, 8, 32, 8, 16, 3, 1, 1, 1, 0, 0, 0, 0, 1, {1, 1, 1}},
+      {"conv3x3 dilated + bwd path.generic=2", G2, 1, 4, 8, 12, 12, 3, 1, 2, 2, 0, 0, 0, 0, 1, {1, 1, 1}},
+      {"deconv 4x4 + bwd (s2d)", {}, 2, 8, 4, 4, 8, 4, 2, 1, 1, 1, 0, 0, 1, 1, {1, 1, 1}},
+      {"deconv 4x4 fp32 + bwd (s2d 32)", F32, 2, 32, 16, 6, 8, 4, 2, 1, 1, 1, 0, 0, 1, 1, {3, 3, 3}},
+      {"deconv 4x4 as conv3x3", {}, 2, 9, 16, 5, 8, 4, 2, 1, 1, 1, 0, 0, 1, 0, {0, 0, 0}},
+      {"deconv 4x4 pad 0 + bwd (generic)", {}, 1, 16, 8, 6, 8, 4, 2, 0, 1, 1, 0, 0, 0, 1, {1, 1, 1}},
+      {"deconv 3x3 adj 1 + bwd", {}, 1, 16, 8, 6, 8, 3, 2, 1, 1, 1, 1, 0, 1, 1, {1, 1, 1}},
+      {"deconv 3x3 adj 1 fp32", F32, 1, 16, 8, 6, 8, 3, 2, 1, 1, 1, 1, 0, 0, 0, {0, 0, 0}},
+      {"conv3x3 packed bf16x3", {}, 1, 8, 32, 8, 16, 3, 1, 1, 1, 0, 0, 1, 1, 0, {0, 0, 0}},
+      {"conv3x3 packed mfma", F32, 1, 8, 32, 8, 16, 3, 1, 1, 1, 0, 0, 1, 1, 0, {0, 0, 0}},
+      {"conv3x3 packed dcm", DCM, 2, 37, 32, 6, 16, 3, 1, 1, 1, 0, 0, 1, 1, 0, {0, 0, 0}},
+      {"deconv 4x4 packed", F32, 2, 9, 16, 5, 8, 4, 2, 1, 1, 1, 0, 1, 1, 0, {0, 0, 0}},
+  };
+  for (const ConvRow &r : convs) conv(r);
+  others();
+  printf("%d calls, %d refused or failed\n", g_calls, g_failed);
+  return g_failed ? 1 : 0;
+}
