@@ -305,6 +305,35 @@ int mfn_flow_metrics(const float *flow, const float *label, const float *mask, f
                      void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Augmentation of the training batch -- replace the device side of the two augmenters that
+ * /root/reference/network/pipeline.py:100-101 applies before every step: GeometryAugmentation
+ * (/root/reference/augmentation.py:229-339) and ColorAugmentation (:168-227).  The per-sample scalars are drawn on the host
+ * (maskflownet_amd/augment.py) and reach the kernels as one small fp32 table per call; maskflownet_amd/csrc/kernels/augment.h
+ * names the table offsets and spells out every fp32 expression in evaluation order (fp contraction off). */
+/* augmentation.py:295-338 in one launch, per target pixel: both affine grids (never stored), the clip of the first, the bilinear
+ * samples of img1 | mask | (flow - shift) * mask through the first and of img2 through the second, flow / max(mask, 1e-8), the
+ * 2x2 re-projection and the grid term.  img1, img2: (N,3,Ho,Wo); flow: (N,2,Ho,Wo) as (u, v); mask: (N,1,Ho,Wo) with
+ * mask_is_plane != 0, else (N,1,1,1) read as a constant plane; table: (N,26).  out1, out2: (N,3,Ht,Wt); flow_out: (N,2,Ht,Wt), written
+ * as (v, u) = (dy, dx) with label_order = 1 (pipeline.py:105); mask_out: (N,1,Ht,Wt).  Ht, Wt >= 2, else MFN_E_SHAPE. */
+int mfn_augment_geometry(const float *img1, const float *img2, const float *flow, const float *mask, int mask_is_plane,
+                         const float *table, float *out1, float *out2, float *flow_out, float *mask_out, int N, int Ho, int Wo,
+                         int Ht, int Wt, int label_order, void *stream);
+/* F.mean of augmentation.py:216 for both images: mean[k,n,c] over the plane of a = M rgb + z * sigma (:213-215), M the
+ * saturation / hue matrix of :198-200 from table (N,26), z the Philox4x32-10 normals of key `seed`, counter (pixel / 4,
+ * (k N + n) 3 + c, offset) -- regenerated, never stored; sigma == 0 runs no generator.  mean: (2N,3).  Fixed summation order
+ * through the caller's workspace as mfn_pair_mean: bit-identical from run to run, at most 46 additions per term. */
+size_t mfn_augment_color_mean_workspace_bytes(int N, int H, int W);
+int mfn_augment_color_mean(const float *img1, const float *img2, const float *table, float sigma, unsigned long long seed,
+                           unsigned long long offset, float *mean, int N, int H, int W, void *workspace, size_t workspace_bytes,
+                           void *stream);
+/* augmentation.py:213-225 element-wise: a as above with the same seed and offset, (a - mean) * contrast * channel, the optional
+ * 3x3 spin (eigen_aug, :220), + (mean * channel + brightness), clip(0, 1), the optional powf(., exp(gamma)) (:224).
+ * out: (2N,3,H,W), images 1 in [0,N), images 2 in [N,2N): the network's input batch layout. */
+int mfn_augment_color(const float *img1, const float *img2, const float *table, const float *mean, float sigma,
+                      unsigned long long seed, unsigned long long offset, int use_spin, int use_gamma, float *out, int N, int H,
+                      int W, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Convolution / Deconvolution -- replace the Gluon blocks of
  * /root/reference/network/MaskFlownet.py:79-163: nn.Conv2D(channels, kernel_size=3, strides, padding, dilation)
  * [+ LeakyReLU(0.1)] of conv() / predict_flow() / predict_mask() (:165-191) and nn.Conv2DTranspose(channels, 4, 2, 1)

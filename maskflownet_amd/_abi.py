@@ -56,6 +56,11 @@ SIGNATURES = {
     "leaky_relu_bwd": (_i, [_f, _f, _f, C.c_size_t, C.c_float, _s]),
     "conv2d_bwd_workspace_bytes": (C.c_size_t, [_i] * 18),
     "conv2d_bwd": (_i, [_f] * 7 + [_i] * 21 + [C.c_void_p, C.c_size_t, _s]),
+    # augmentation of the training batch (kernels/augment.h); bound by the emulation build as well
+    "augment_geometry": (_i, [_f, _f, _f, _f, _i, _f, _f, _f, _f, _f] + [_i] * 6 + [_s]),
+    "augment_color_mean_workspace_bytes": (C.c_size_t, [_i] * 3),
+    "augment_color_mean": (_i, [_f, _f, _f, C.c_float, C.c_ulonglong, C.c_ulonglong, _f] + [_i] * 3 + [C.c_void_p, C.c_size_t, _s]),
+    "augment_color": (_i, [_f, _f, _f, _f, C.c_float, C.c_ulonglong, C.c_ulonglong, _i, _i, _f] + [_i] * 3 + [_s]),
     "set_arithmetic": (_i, [C.c_char_p, _i]),
     "get_arithmetic": (_i, [C.c_char_p, _pi]),
     "set_tuning": (_i, [C.c_char_p, _i]),

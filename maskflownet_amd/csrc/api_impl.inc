@@ -19,6 +19,7 @@
 #include "kernels/warp.h"
 #include "kernels/upsample.h"
 #include "kernels/predict.h"
+#include "kernels/augment.h"
 #include "kernels/backward.h"
 #include "kernels/dc_backward.h"
 #include "kernels/conv.h"
@@ -907,6 +908,75 @@ int MFN_API(flow_metrics)(const float *flow, const float *label, const float *ma
   if (!aligned(workspace, 4)) return fail(MFN_E_ALIGN, "flow_metrics: workspace must be 4-byte aligned");
   FlowMetricsParams p{flow, label, mask, (float *)workspace, sums, plane, N, slices};
   return hipfail(flow_metrics_launch(p, (hipStream_t)stream), "flow_metrics");
+}
+
+// ---- augmentation of the training batch: geometry, colour (kernels/augment.h) ---------------------------------------------
+static int augment_color_dims(const char *what, int N, int H, int W) {
+  if (N < 0 || H <= 0 || W <= 0) return fail(MFN_E_SHAPE, "%s: N=%d H=%d W=%d", what, N, H, W);
+  if ((size_t)2 * N > 65535 || (size_t)6 * N * (size_t)H * W >= ((size_t)1 << 32)) return fail(MFN_E_UNSUPPORTED, "%s: tensor too large", what);
+  return reduce_dims(what, (size_t)2 * N, (size_t)H * W);
+}
+static AugNoise augment_noise(unsigned long long seed, unsigned long long offset) {
+  return AugNoise{(unsigned)seed, (unsigned)(seed >> 32), (unsigned)offset, (unsigned)(offset >> 32)};
+}
+
+int MFN_API(augment_geometry)(const float *img1, const float *img2, const float *flow, const float *mask, int mask_is_plane,
+                              const float *table, float *out1, float *out2, float *flow_out, float *mask_out, int N, int Ho, int Wo,
+                              int Ht, int Wt, int label_order, void *stream) {
+  if (N != 0 && (!img1 || !img2 || !flow || !mask || !table || !out1 || !out2 || !flow_out || !mask_out))
+    return fail(MFN_E_NULL, "augment_geometry: NULL tensor pointer");
+  if (N < 0 || Ho <= 0 || Wo <= 0 || Ht < 2 || Wt < 2)
+    return fail(MFN_E_SHAPE, "augment_geometry: N=%d Ho=%d Wo=%d Ht=%d Wt=%d (a target side must be >= 2)", N, Ho, Wo, Ht, Wt);
+  if ((size_t)Ho * Wo >= ((size_t)1 << 31) || (size_t)N * Ht * Wt >= ((size_t)1 << 31))
+    return fail(MFN_E_UNSUPPORTED, "augment_geometry: tensor too large");
+  if (N == 0) return 0;
+  AugGeoParams p{};
+  p.img1 = img1; p.img2 = img2; p.flow = flow; p.mask = mask; p.tab = table;
+  p.o1 = out1; p.o2 = out2; p.oflow = flow_out; p.omask = mask_out;
+  p.N = N; p.Ho = Ho; p.Wo = Wo; p.Ht = Ht; p.Wt = Wt;
+  p.mask_plane = mask_is_plane ? 1 : 0;
+  p.label_order = label_order ? 1 : 0;
+  p.sx = (float)(2.0 / (Wt - 1));
+  p.sy = (float)(2.0 / (Ht - 1));
+  p.st_policy = store_policy_for(settings_now(), (size_t)N * 9 * Ht * Wt * 4, 2, -1);
+  return hipfail(augment_geometry_launch(p, (hipStream_t)stream), "augment_geometry");
+}
+
+size_t MFN_API(augment_color_mean_workspace_bytes)(int N, int H, int W) {
+  if (N <= 0 || H <= 0 || W <= 0) return 0;
+  return (size_t)2 * N * pred_slices((size_t)H * W) * 3 * sizeof(float);
+}
+
+int MFN_API(augment_color_mean)(const float *img1, const float *img2, const float *table, float sigma, unsigned long long seed,
+                                unsigned long long offset, float *mean, int N, int H, int W, void *workspace, size_t workspace_bytes,
+                                void *stream) {
+  if (N != 0 && (!img1 || !img2 || !table || !mean)) return fail(MFN_E_NULL, "augment_color_mean: NULL tensor pointer");
+  if (int rc = augment_color_dims("augment_color_mean", N, H, W)) return rc;
+  if (N == 0) return 0;
+  const size_t plane = (size_t)H * W;
+  const int slices = pred_slices(plane);
+  const size_t need = (size_t)2 * N * slices * 3 * sizeof(float);
+  if (!workspace || workspace_bytes < need)
+    return fail(MFN_E_WORKSPACE, "augment_color_mean: workspace of %zu bytes needed, %zu given", need, workspace ? workspace_bytes : (size_t)0);
+  if (!aligned(workspace, 4)) return fail(MFN_E_ALIGN, "augment_color_mean: workspace must be 4-byte aligned");
+  AugColorParams p{};
+  p.img1 = img1; p.img2 = img2; p.tab = table; p.partial = (float *)workspace; p.mean = mean;
+  p.plane = plane; p.N = N; p.slices = slices; p.sigma = sigma; p.noise = augment_noise(seed, offset);
+  return hipfail(augment_color_mean_launch(p, (hipStream_t)stream), "augment_color_mean");
+}
+
+int MFN_API(augment_color)(const float *img1, const float *img2, const float *table, const float *mean, float sigma,
+                           unsigned long long seed, unsigned long long offset, int use_spin, int use_gamma, float *out, int N, int H,
+                           int W, void *stream) {
+  if (N != 0 && (!img1 || !img2 || !table || !mean || !out)) return fail(MFN_E_NULL, "augment_color: NULL tensor pointer");
+  if (int rc = augment_color_dims("augment_color", N, H, W)) return rc;
+  if (N == 0) return 0;
+  AugColorParams p{};
+  p.img1 = img1; p.img2 = img2; p.tab = table; p.mean_in = mean; p.out = out;
+  p.plane = (size_t)H * W; p.N = N; p.sigma = sigma; p.noise = augment_noise(seed, offset);
+  p.spin = use_spin ? 1 : 0; p.gamma = use_gamma ? 1 : 0;
+  p.st_policy = store_policy_for(settings_now(), (size_t)6 * N * H * W * 4, 2, -1);
+  return hipfail(augment_color_launch(p, (hipStream_t)stream), "augment_color");
 }
 
 // ---- backward (SURVEY.md 8 a7) -------------------------------------------------------------------------------

@@ -523,6 +523,72 @@ class OpSet:
         s = self.flow_metric_sums(flow, label, mask)
         return s[:, 0] / s[:, 1], s[:, 2] / s[:, 1]
 
+    # ---- augmentation of the training batch (augmentation.py:168-339, as pipeline.py:100-101 applies it) --------------------------
+    def augment_geometry(self, img1, img2, flow, mask, table, target_shape, label_order=0, out=None):
+        """GeometryAugmentation.hybrid_forward (augmentation.py:295-338) in one launch.  img1, img2 (N,3,Ho,Wo); flow (N,2,Ho,Wo)
+        as (u, v); mask (N,1,Ho,Wo) or (N,1,1,1) (a constant plane, never materialised); table (N,26) per kernels/augment.h.
+        -> (img1', img2', flow', mask') at target_shape; label_order=1 writes the flow as (dy, dx) (pipeline.py:105).
+        out: the four destinations."""
+        a, b, f, m, t = self._in(img1, img2, flow, mask, table)
+        if self.ad.ndim(a) != 4 or self.ad.shape(a)[1] != 3 or self.ad.shape(b) != self.ad.shape(a):
+            raise ValueError("augment_geometry: img1 and img2 must both be (N,3,H,W), got %s and %s" % (self.ad.shape(a), self.ad.shape(b)))
+        N, _, Ho, Wo = self.ad.shape(a)
+        if self.ad.shape(f) != (N, 2, Ho, Wo):
+            raise ValueError("augment_geometry: flow must have shape %s, got %s" % ((N, 2, Ho, Wo), self.ad.shape(f)))
+        if self.ad.shape(m) not in ((N, 1, Ho, Wo), (N, 1, 1, 1)):
+            raise ValueError("augment_geometry: mask must have shape %s or %s, got %s" % ((N, 1, Ho, Wo), (N, 1, 1, 1), self.ad.shape(m)))
+        if self.ad.shape(t) != (N, 26):
+            raise ValueError("augment_geometry: table must have shape %s, got %s" % ((N, 26), self.ad.shape(t)))
+        Ht, Wt = (int(v) for v in target_shape)
+        o = out if out is not None else (None,) * 4
+        if len(o) != 4:
+            raise ValueError("augment_geometry: out must hold four destinations")
+        o1 = self._out(o[0], a, (N, 3, Ht, Wt), "augment_geometry img1")
+        o2 = self._out(o[1], a, (N, 3, Ht, Wt), "augment_geometry img2")
+        of = self._out(o[2], a, (N, 2, Ht, Wt), "augment_geometry flow")
+        om = self._out(o[3], a, (N, 1, Ht, Wt), "augment_geometry mask")
+        self.check(self.ns.augment_geometry(self.ad.ptr(a), self.ad.ptr(b), self.ad.ptr(f), self.ad.ptr(m),
+                                            int(self.ad.shape(m) == (N, 1, Ho, Wo)), self.ad.ptr(t), self.ad.ptr(o1), self.ad.ptr(o2),
+                                            self.ad.ptr(of), self.ad.ptr(om), N, Ho, Wo, Ht, Wt, int(bool(label_order)),
+                                            self.ad.stream(a)))
+        return o1, o2, of, om
+
+    def _color_args(self, what, img1, img2, table):
+        a, b, t = self._in(img1, img2, table)
+        if self.ad.ndim(a) != 4 or self.ad.shape(a)[1] != 3 or self.ad.shape(b) != self.ad.shape(a):
+            raise ValueError("%s: img1 and img2 must both be (N,3,H,W), got %s and %s" % (what, self.ad.shape(a), self.ad.shape(b)))
+        if self.ad.shape(t) != (self.ad.shape(a)[0], 26):
+            raise ValueError("%s: table must have shape %s, got %s" % (what, (self.ad.shape(a)[0], 26), self.ad.shape(t)))
+        return a, b, t
+
+    def augment_color_mean(self, img1, img2, table, sigma=0.0, seed=0, offset=0, out=None):
+        """The per (image, sample, channel) mean of augmentation.py:216 over a = M rgb + noise * sigma: -> (2N,3), fixed summation
+        order.  seed, offset: the 64-bit Philox key and the call counter; sigma == 0 uses neither."""
+        a, b, t = self._color_args("augment_color_mean", img1, img2, table)
+        N, _, H, W = self.ad.shape(a)
+        out = self._out(out, a, (2 * N, 3), "augment_color_mean")
+        ws = self._workspace(a, self.ns.augment_color_mean_workspace_bytes(N, H, W))
+        self.check(self.ns.augment_color_mean(self.ad.ptr(a), self.ad.ptr(b), self.ad.ptr(t), float(sigma), int(seed) & (2 ** 64 - 1),
+                                              int(offset) & (2 ** 64 - 1), self.ad.ptr(out), N, H, W, self.ad.ptr(ws), self.ad.nbytes(ws),
+                                              self.ad.stream(a)))
+        return out
+
+    def augment_color(self, img1, img2, table, sigma=0.0, seed=0, offset=0, spin=False, gamma=False, mean=None, out=None):
+        """ColorAugmentation.hybrid_forward (augmentation.py:213-225) for both images: -> (2N,3,H,W), images 1 first.  mean: (2N,3),
+        default augment_color_mean with the same table, sigma, seed and offset."""
+        a, b, t = self._color_args("augment_color", img1, img2, table)
+        N, _, H, W = self.ad.shape(a)
+        if mean is None:
+            mean = self.augment_color_mean(a, b, t, sigma, seed, offset)
+        (m,) = self._in(mean)
+        if self.ad.shape(m) != (2 * N, 3):
+            raise ValueError("augment_color: mean must have shape %s, got %s" % ((2 * N, 3), self.ad.shape(m)))
+        out = self._out(out, a, (2 * N, 3, H, W), "augment_color")
+        self.check(self.ns.augment_color(self.ad.ptr(a), self.ad.ptr(b), self.ad.ptr(t), self.ad.ptr(m), float(sigma),
+                                         int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), int(bool(spin)), int(bool(gamma)),
+                                         self.ad.ptr(out), N, H, W, self.ad.stream(a)))
+        return out
+
     def Upsample_backward(self, out_grad, factor, req="write", out=None):
         """Adjoint of Upsample(factor): (N,C,H*f,W*f) -> (N,C,H,W) (mfn_upsample_bwd)."""
         (go,) = self._in(out_grad)
@@ -911,6 +977,18 @@ def flow_metric_sums(*a, **k):
 
 def flow_metrics(*a, **k):
     return default_ops().flow_metrics(*a, **k)
+
+
+def augment_geometry(*a, **k):
+    return default_ops().augment_geometry(*a, **k)
+
+
+def augment_color_mean(*a, **k):
+    return default_ops().augment_color_mean(*a, **k)
+
+
+def augment_color(*a, **k):
+    return default_ops().augment_color(*a, **k)
 
 
 def Convolution(*a, **k):

@@ -329,3 +329,40 @@ def train_step(net, loss_fn, opt, im1, im2, label, mask, buckets=None, global_ba
                 p.grad.mul_(1.0 / gb)
     opt.step()
     return loss.detach()
+
+
+def augment_batch(img1, img2, label, mask, geo_aug, color_aug):
+    """pipeline.py:99-105 on the device: `/ 255`, the geometry augmenter (the flow comes back flipped to the network's (dy, dx) order,
+    :105), the colour augmenter, `centralize` (ops.pair_mean + ops.preprocess_pair at equal size: x - rgb_mean).  img1, img2: (N,3,H,W)
+    uint8 or float in 0..255; label: (N,2,H,W) in the reader's (u, v) order; mask: (N,1,H,W) or (N,1,1,1) in 0..255, None = all valid
+    (:93-94).  -> (batch (2N,3,Ht,Wt) with images 1 first, label (N,2,Ht,Wt), mask (N,1,Ht,Wt))."""
+    N = img1.shape[0]
+    if mask is None:
+        mask = torch.full((N, 1, 1, 1), 255.0, device=img1.device)
+    im1, im2, msk = (t.to(torch.float32) / 255.0 for t in (img1, img2, mask))
+    im1, im2, lab, msk = geo_aug(im1, im2, label.to(torch.float32), msk, label_order=1)
+    both = color_aug(im1, im2)
+    H, W = both.shape[2:]
+    return ops.preprocess_pair(both[:N], both[N:], H, W, mean=ops.pair_mean(both[:N], both[N:])), lab, msk
+
+
+def train_batch(net, loss_fn, opt, img1, img2, label, mask, geo_aug, color_aug, buckets=None, global_batch=None):
+    """pipeline.py:89-115: augment_batch, then train_step itself; the finest prediction of its one forward pass is picked up by a
+    forward hook that lives for this call.  Returns (the per-sample loss of the local shard, the masked end-point error of :107 per
+    sample)."""
+    x, lab, msk = augment_batch(img1, img2, label, mask, geo_aug, color_aug)
+    N = lab.shape[0]
+    finest = []
+
+    def keep(mod, args, out):   # the trainable networks return (predictions, coarse to fine; further outputs): train_step's `preds, _ = net(..)`
+        preds = out[0]
+        if not isinstance(preds, (list, tuple)) or not torch.is_tensor(preds[-1]):
+            raise TypeError("train_batch: net must return (a sequence of flow predictions, coarse to fine; ...), as the trainable networks do")
+        finest.append(preds[-1].detach())
+    hook = net.register_forward_hook(keep)
+    try:
+        loss = train_step(net, loss_fn, opt, x[:N], x[N:], lab, msk, buckets=buckets, global_batch=global_batch)
+    finally:
+        hook.remove()
+    epe, _ = ops.flow_metrics(ops.Upsample(finest[-1], loss_fn.scales[-1]), lab, msk)
+    return loss, epe
