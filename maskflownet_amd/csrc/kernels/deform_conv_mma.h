@@ -34,7 +34,7 @@
 //   * lanes whose neighbourhood falls outside the wave's 12 x 20 window (2 % of the tiles of the bench flows; before: the
 //     whole tile fell to the slower global-gather tier and its block finished ~4 us after the others) fetch their 16 values
 //     from global memory under an exec mask, everybody else keeps the window;
-//   * the K-slice reduction and the epilogue run on the waves in parallel (tile mt is summed and stored by slice mt % KW).
+//   * the K-slice reduction and the epilogue run on every wave (each sums and stores a slab of the pixel tile's filter rows).
 // Per-tap offsets (MXNet's general semantics, never hot in the reference) take a lean per-tap column path inside the same kernel.
 #pragma once
 #include "deform_conv.h"
@@ -116,15 +116,22 @@ template <int MT, int PT, int KW, int RING> struct DcmGeom {
   static constexpr int NI = (WI_TOTAL + NW - 1) / NW;  // ... per wave at most; a wave whose last one would be past WI_TOTAL issues one fewer
   static constexpr int NI_MIN = WI_TOTAL / NW;         // ... at least: the waits count with this (a wave that issued one more waits for it too)
   static constexpr int STAGE_W = WI_TOTAL * 256;       // words per stage buffer
-  // K-slice reduction through the (then idle) stage buffers: every slice's MT tiles at once where they fit -- one barrier --, else
-  // tile by tile (one 32 x 32 tile per non-owner slice, two barriers per tile)
-  static constexpr bool RED_ALL = KW > 1 && PT * KW * MT * 1024 <= NSTAGE * STAGE_W;
-  static constexpr int RED_W = KW > 1 ? (RED_ALL ? PT * KW * MT * 1024 : PT * (KW - 1) * 1024) : 0;
-  static constexpr int XW_OFF = NSTAGE * STAGE_W > RED_W ? NSTAGE * STAGE_W : RED_W;
+  static constexpr int XW_OFF = NSTAGE * STAGE_W;
   static constexpr int T8_OFF = XW_OFF + NW * RING * DCM_XW_F;      // tap 8 of a group's eight pairs: [wave][pair][lane]
   static constexpr int DUMP_OFF = T8_OFF + NW * 512;
   static constexpr int LDS_W = DUMP_OFF + 256;
   static_assert(LDS_W * 4 <= 160 * 1024, "a block's LDS must fit the CU");
+  // K-slice reduction: behind the loop nothing of the block's LDS is in use any more (stage buffers, window rings, tap-8 slots), and
+  // every slice's MT partial tiles lie in it at once, from word 0: [pt][kw][mt][32 filter rows][RED_TS], the epilogue's transposed form
+  // (a lane reads four adjacent pixels of a filter row with one 16-byte read; a D register's two half-waves write rows 4 apart,
+  // 160 = 32 mod 64 words: disjoint banks)
+  static constexpr int RED_TS = 40, RED_TILE = 32 * RED_TS;
+  static constexpr int RED_W = KW > 1 ? PT * KW * MT * RED_TILE : 0;
+  static_assert(RED_W <= DUMP_OFF, "every slice's partial tiles fit the block's LDS at once");
+  // ... summed and stored by ALL KW waves of the pixel tile: wave kw takes the slab [kw RED_SLAB, (kw + 1) RED_SLAB) of the 32 MT
+  // filter rows, eight rows -- one per eight lanes -- at a time (a slab of four rows: half the wave)
+  static constexpr int RED_ROWS = 32 * MT, RED_SLAB = RED_ROWS / KW, RED_PASSES = (RED_SLAB + 7) / 8;
+  static_assert(RED_ROWS % KW == 0, "the K slices divide the tile's filter rows evenly (every shipped tiling; an uneven split needs a clipped last slab)");
 };
 
 // s_waitcnt vmcnt count at the head of step s (0..8) of a group, from a simulation of the periodic issue sequence: a step
@@ -181,18 +188,6 @@ template <int KC, int NSTAGE, int RING, int NI, int XW_NI> constexpr unsigned dc
     m |= 1u << q;
   }
   return m;
-}
-
-// transfers the prologue issues after window 0: what may still be outstanding when pair 0 is gathered
-template <int KC, int NSTAGE, int RING, int NI, int XW_NI> constexpr int dcm_prologue_after_x0() {
-  int issued = 0, at_x0 = -1;
-  for (int u = -36; u < 0; ++u) {
-    const int ss = ((u % 9) + 9) % 9;
-    const int kl = (u - ss) / 9 * 8 + ss;
-    if (ss % KC == 0 && u / KC + NSTAGE - 1 >= 0) issued += NI;
-    if (ss < 8 && kl + RING >= 0) { issued += XW_NI; if (kl + RING == 0) at_x0 = issued; }
-  }
-  return issued - at_x0;
 }
 
 // weights (Cout, Cin, 9) -> packed[mg][grp][s 0..8][term h|m|l][ft][kb][m 0..31][e 0..7] bf16; filter o = (mg * MT + ft) * 32 + m;
@@ -284,6 +279,13 @@ __global__ __launch_bounds__(PT * KW * 64, MFN_DCM_MINW(MT, PT * KW)) void dc_mm
       if (ii < G::WI_TOTAL) mfn_dma16_so(wrsrc, buf + ii * 256, voffW[i], soff);   // wave-uniform
     }
   };
+
+  // The prologue's weight chunks (0 .. NSTAGE - 2) depend on nothing below: they are requested HERE, ahead of the offset loads, so
+  // that their way from memory lies under the offsets' round trip, the geometry and the window box instead of behind them.
+  // (Transfers complete in issue order: hipcc's own wait for the offset loads, which it counts, covers these older transfers
+  // too -- the offsets are then back when chunk 0 is, not before.)
+  MFN_UNROLL
+  for (int ch = 0; ch < G::NSTAGE - 1; ++ch) issue_w(ch);
 
   // ---- the wave's pixel tile: 4 rows x 8 columns of one image ---------------------------------------------------------
   int n, ty, tx;
@@ -464,7 +466,7 @@ __global__ __launch_bounds__(PT * KW * 64, MFN_DCM_MINW(MT, PT * KW)) void dc_mm
     buf_issue = buf_issue + 1 == WN::DEPTH ? 0 : buf_issue + 1;
   };
 
-  // ---- prologue: what the steps before the first would have issued, in their order (chunks 0 .. NSTAGE - 2, windows 0 .. DEPTH - 1) ----
+  // ---- prologue: the windows the steps before the first would have issued (0 .. DEPTH - 1) ----
   auto prologue = [&](auto win_c) {
     using WN = decltype(win_c);
     constexpr int U0 = -9 * 4;   // far enough back for every prefetch distance
@@ -472,8 +474,7 @@ __global__ __launch_bounds__(PT * KW * 64, MFN_DCM_MINW(MT, PT * KW)) void dc_mm
     for (int u = U0; u < 0; ++u) {
       const int ss = ((u % 9) + 9) % 9;
       const int kl = (u - ss) / 9 * 8 + ss;                                  // pair of step u (ss < 8)
-      if (ss % KC == 0 && (u - ss % KC) / KC + G::NSTAGE - 1 >= 0) issue_w((u - ss % KC) / KC + G::NSTAGE - 1);
-      if (ss < 8 && kl + WN::DEPTH >= 0) issue_x(kl + WN::DEPTH, win_c);
+      if (ss < 8 && kl + WN::DEPTH >= 0) issue_x(kl + WN::DEPTH, win_c);   // (the chunks of these steps: requested above)
     }
   };
   MFN_STAMP2(p.timeline, 2);   // window box
@@ -670,15 +671,19 @@ __global__ __launch_bounds__(PT * KW * 64, MFN_DCM_MINW(MT, PT * KW)) void dc_mm
   float *xt8 = lds + G::T8_OFF + wave * 512 + lane;   // tap 8 of the group's eight pairs, [pair][lane]: the left-over step's K elements
   auto first_operand = [&](auto win_c, auto out_c) {
     using WN = decltype(win_c);
-    MFN_WAIT_VM((dcm_prologue_after_x0<KC, G::NSTAGE, WN::DEPTH, NIW, WN::NI>()));   // window 0 landed
+    // Everything the prologue issued has landed -- not window 0 alone: the loop's counts (dcm_wait_count) are those of the steady
+    // sequence, in which a step's weight chunk is issued between windows; with the prologue's chunks AHEAD of its windows fewer
+    // transfers follow window k than the count of the step that gathers it allows to be outstanding.  (Windows 1 .. DEPTH - 1 were
+    // issued back to back with window 0.)
+    MFN_WAIT_VM(0);
     float x8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, c8 = 0.f;
     if (fast) {
       if (decltype(out_c)::value) lanes_request(0, std::integral_constant<int, 1>{});
       cols_gather(0, win_c);
       if (decltype(out_c)::value) {
         lanes_landed(std::integral_constant<int, 1>{}, std::integral_constant<int, 0>{});
-        // the pair the loop's first step prepares.  (The wait above was for EVERYTHING the prologue issued: the loop's counts
-        // assume the steady sequence, requests included, which the prologue does not replay.)
+        // the pair the loop's first step prepares (its requests too are counted by the loop as in the steady sequence: nothing of
+        // this pair's requests is outstanding behind lanes_landed above)
         lanes_request(1, std::integral_constant<int, 0>{});
       }
       cols_finish(x8, c8);
@@ -797,81 +802,16 @@ __global__ __launch_bounds__(PT * KW * 64, MFN_DCM_MINW(MT, PT * KW)) void dc_mm
   MFN_STAMP_INFO(p.timeline, !fast ? 3 : (!bigwin ? 0 : (all_in ? 1 : 2)));   // the first wave's tier
 
   MFN_STAMP2(p.timeline, 5);
-  // ---- K-slice reduction: tile mt is summed (slice order 0..KW-1, deterministic) and stored by slice mt % KW ------------------------
   MFN_WAIT_VM(0);       // the prefetches past the end have landed: nothing is on its way into LDS any more
   f32x16 fin[MT];
   MFN_UNROLL
   for (int mt = 0; mt < MT; ++mt)
     MFN_UNROLL
     for (int r = 0; r < 16; ++r) fin[mt][r] = NACC == 2 ? acc[mt][0][r] + acc[mt][NACC - 1][r] : acc[mt][0][r];
-  if (KW > 1) {
-    MFN_WAIT_LGKM0();
-    MFN_RAW_BARRIER();  // every wave is out of the loop: the stage buffers are free
-    if (G::RED_ALL) {   // every slice's tiles at once: [pt][kw][mt][16][64]
-      float *mine = lds + (size_t)((pt * KW + kw) * MT) * 1024 + lane;
-      MFN_UNROLL
-      for (int mt = 0; mt < MT; ++mt)
-        if (kw != mt % KW) {
-          MFN_UNROLL
-          for (int r = 0; r < 16; ++r) mine[mt * 1024 + r * 64] = fin[mt][r];
-        }
-      __syncthreads();
-      MFN_UNROLL
-      for (int mt = 0; mt < MT; ++mt) {
-        const int owner = mt % KW;
-        if (kw != owner) continue;
-        f32x16 sum;
-        MFN_UNROLL
-        for (int k = 0; k < KW; ++k) {
-          f32x16 part;
-          if (k == owner) part = fin[mt];
-          else {
-            const float *src = lds + (size_t)((pt * KW + k) * MT + mt) * 1024 + lane;
-            MFN_UNROLL
-            for (int r = 0; r < 16; ++r) part[r] = src[r * 64];
-          }
-          MFN_UNROLL
-          for (int r = 0; r < 16; ++r) sum[r] = k == 0 ? part[r] : sum[r] + part[r];
-        }
-        fin[mt] = sum;
-      }
-    } else {
-      float *red = lds + (size_t)pt * (KW - 1) * 1024;
-      MFN_UNROLL
-      for (int mt = 0; mt < MT; ++mt) {
-        const int owner = mt % KW;
-        if (kw != owner) {
-          float *dst = red + (size_t)(kw < owner ? kw : kw - 1) * 1024 + lane;
-          MFN_UNROLL
-          for (int r = 0; r < 16; ++r) dst[r * 64] = fin[mt][r];
-        }
-        __syncthreads();
-        if (kw == owner) {
-          f32x16 sum;
-          MFN_UNROLL
-          for (int k = 0; k < KW; ++k) {
-            f32x16 part;
-            if (k == owner) part = fin[mt];
-            else {
-              const float *src = red + (size_t)(k < owner ? k : k - 1) * 1024 + lane;
-              MFN_UNROLL
-              for (int r = 0; r < 16; ++r) part[r] = src[r * 64];
-            }
-            MFN_UNROLL
-            for (int r = 0; r < 16; ++r) sum[r] = k == 0 ? part[r] : sum[r] + part[r];
-          }
-          fin[mt] = sum;
-        }
-        if (mt + 1 < MT) __syncthreads();
-      }
-    }
-  }
 
-  MFN_STAMP2(p.timeline, 6);   // K slices reduced
-  // ---- epilogue.  D reg r of lane (j, kb): filter row (r&3) + 8*(r>>2) + 4*kb, pixel j.  The 32 x 32 tile is transposed through
-  // the wave's idle window ring so that a lane holds four adjacent pixels of one filter: 4 x 16-byte stores instead of 16 dword stores
-  constexpr int TS = 40;
-  float *tr = xwin;
+  // ---- epilogue geometry.  D reg r of lane (j, kb): filter row (r&3) + 8*(r>>2) + 4*kb, pixel j.  A 32 x 32 tile is transposed through
+  // LDS so that a lane holds four adjacent pixels of one filter row: 16-byte stores, eight lanes a row, eight rows a wave
+  constexpr int TS = G::RED_TS;
   const size_t oplane = plane;
   const int quad = lane & 7, orow = lane >> 3;
   const int px0 = quad * 4;
@@ -883,56 +823,110 @@ __global__ __launch_bounds__(PT * KW * 64, MFN_DCM_MINW(MT, PT * KW)) void dc_mm
   MFN_UNROLL
   for (int q = 0; q < 4; ++q) oxq[q] = st_ok ? min(ox + q, W - 1) : 0;
   float sg[4] = {1.f, 1.f, 1.f, 1.f};
-  if (ep && p.ep_mask) {
-    float mv[4];
-    MFN_UNROLL
-    for (int q = 0; q < 4; ++q) mv[q] = p.ep_mask[pix0 + oxq[q]];
-    MFN_UNROLL
-    for (int q = 0; q < 4; ++q) sg[q] = 1.f / (1.f + expf(-mv[q]));
-  }
   const size_t obatch = st_ok ? (size_t)n * p.Cout * oplane + (size_t)oy * W : 0;
   float *obase = p.out + (size_t)n * (p.out_nstride ? p.out_nstride : (size_t)p.Cout * oplane);
-  MFN_UNROLL
-  for (int mt = 0; mt < MT; ++mt) {
-    if (KW > 1 && kw != mt % KW) continue;
-    float bq[4], addv[4][4];
+  // bias, the optional mask / add / leaky epilogue and the store of filter o's four pixels
+  auto finish_row = [&](int o, const float4 &v, float bv, const float (&av)[4], bool live) {
+    float e[4] = {v.x + bv, v.y + bv, v.z + bv, v.w + bv};
+    if (ep) {
+      MFN_UNROLL
+      for (int q = 0; q < 4; ++q) {
+        if (p.ep_mask) e[q] = e[q] * sg[q];
+        if (p.ep_add) e[q] = e[q] + av[q];
+        if (p.ep_leaky) e[q] = fmaxf(e[q], 0.1f * e[q]);
+      }
+    }
+    if (live && st_ok && o < p.Cout) {
+      float *dst = obase + (size_t)o * oplane + (size_t)oy * W + ox;
+      if (ox + 3 < W) {
+        mfn_store4_stream(dst, e[0], e[1], e[2], e[3], p.st_policy);
+      } else {
+        MFN_UNROLL
+        for (int q = 0; q < 4; ++q)
+          if (ox + q < W) dst[q] = e[q];
+      }
+    }
+  };
+
+  if constexpr (KW > 1) {
+    // ---- K-slice reduction + epilogue on every wave: each slice hands its MT partial tiles over in the transposed form (G::RED_*),
+    // then wave kw sums its slab of the pixel tile's filter rows over the slices -- slice order 0..KW-1, the order the sum always
+    // had -- and stores it.  (Before: tile mt was summed and stored by slice mt % KW alone -- at (MT, KW) = (1, 8) one wave read
+    // seven tiles with 112 ds_read_b32, added, transposed through LDS and stored while seven waited.)
+    const int row_lo = kw * G::RED_SLAB;
+    // what the slab's rows take from memory is requested before the tiles change hands; its first use is behind the barriers
+    float mv[4] = {0.f, 0.f, 0.f, 0.f};
+    if (ep && p.ep_mask) {
+      MFN_UNROLL
+      for (int q = 0; q < 4; ++q) mv[q] = p.ep_mask[pix0 + oxq[q]];
+    }
+    float bq[G::RED_PASSES], addv[G::RED_PASSES][4];
     MFN_UNROLL
-    for (int i = 0; i < 4; ++i) bq[i] = p.bias ? p.bias[min(m0 + mt * 32 + i * 8 + orow, p.Cout - 1)] : 0.f;
-    if (ep && p.ep_add) {
+    for (int i = 0; i < G::RED_PASSES; ++i) {
+      const int oc = min(m0 + row_lo + i * 8 + orow, p.Cout - 1);
+      bq[i] = p.bias ? p.bias[oc] : 0.f;
+      MFN_UNROLL
+      for (int q = 0; q < 4; ++q) addv[i][q] = (ep && p.ep_add) ? p.ep_add[obatch + (size_t)oc * oplane + oxq[q]] : 0.f;
+    }
+    MFN_LDS_BARRIER();  // every wave is out of the loop: stage buffers, window rings and tap-8 slots are free
+    float *mine = lds + (size_t)((pt * KW + kw) * MT) * G::RED_TILE + j;
+    MFN_UNROLL
+    for (int mt = 0; mt < MT; ++mt)
+      MFN_UNROLL
+      for (int r = 0; r < 16; ++r) mine[mt * G::RED_TILE + ((r & 3) + 8 * (r >> 2) + 4 * kb) * TS] = fin[mt][r];
+    MFN_LDS_BARRIER();
+    MFN_STAMP2(p.timeline, 6);   // K slices' partial tiles handed over
+    if (ep && p.ep_mask) {
+      MFN_UNROLL
+      for (int q = 0; q < 4; ++q) sg[q] = 1.f / (1.f + expf(-mv[q]));
+    }
+    const float *slab = lds + (size_t)(pt * KW * MT) * G::RED_TILE + px0;
+    MFN_UNROLL
+    for (int i = 0; i < G::RED_PASSES; ++i) {
+      const int row = row_lo + i * 8 + orow;   // filter row of the M-group: tile row >> 5, line row & 31 -- consecutive in the layout
+      const bool live = i * 8 + orow < G::RED_SLAB;
+      float4 s = {0.f, 0.f, 0.f, 0.f};
+      if (live) {
+        MFN_UNROLL
+        for (int k = 0; k < KW; ++k) {
+          const float4 v = *reinterpret_cast<const float4 *>(slab + (size_t)k * (MT * G::RED_TILE) + row * TS);
+          if (k == 0) s = v;
+          else { s.x = s.x + v.x; s.y = s.y + v.y; s.z = s.z + v.z; s.w = s.w + v.w; }
+        }
+      }
+      finish_row(m0 + row, s, bq[i], addv[i], live);
+    }
+  } else {
+    MFN_STAMP2(p.timeline, 6);
+    // ---- one K slice: the wave transposes its own tiles through its idle window ring
+    float *tr = xwin;
+    if (ep && p.ep_mask) {
+      float mv[4];
+      MFN_UNROLL
+      for (int q = 0; q < 4; ++q) mv[q] = p.ep_mask[pix0 + oxq[q]];
+      MFN_UNROLL
+      for (int q = 0; q < 4; ++q) sg[q] = 1.f / (1.f + expf(-mv[q]));
+    }
+    MFN_UNROLL
+    for (int mt = 0; mt < MT; ++mt) {
+      float bq[4], addv[4][4];
+      MFN_UNROLL
+      for (int i = 0; i < 4; ++i) bq[i] = p.bias ? p.bias[min(m0 + mt * 32 + i * 8 + orow, p.Cout - 1)] : 0.f;
       MFN_UNROLL
       for (int i = 0; i < 4; ++i) {
         const size_t orow_off = obatch + (size_t)min(m0 + mt * 32 + i * 8 + orow, p.Cout - 1) * oplane;
         MFN_UNROLL
-        for (int q = 0; q < 4; ++q) addv[i][q] = p.ep_add[orow_off + oxq[q]];
+        for (int q = 0; q < 4; ++q) addv[i][q] = (ep && p.ep_add) ? p.ep_add[orow_off + oxq[q]] : 0.f;
       }
-    }
-    MFN_WAIT_LGKM0();   // the previous tile's reads are done (wave-private buffer: no barrier needed)
-    MFN_UNROLL
-    for (int r = 0; r < 16; ++r) tr[((r & 3) + 8 * (r >> 2) + 4 * kb) * TS + j] = fin[mt][r];
-    MFN_WAIT_LGKM0();
-    MFN_UNROLL
-    for (int i = 0; i < 4; ++i) {
-      const int ol = i * 8 + orow;
-      const int o = m0 + mt * 32 + ol;
-      const float4 v = *reinterpret_cast<const float4 *>(tr + ol * TS + px0);
-      float e[4] = {v.x + bq[i], v.y + bq[i], v.z + bq[i], v.w + bq[i]};
-      if (ep) {
-        MFN_UNROLL
-        for (int q = 0; q < 4; ++q) {
-          if (p.ep_mask) e[q] = e[q] * sg[q];
-          if (p.ep_add) e[q] = e[q] + addv[i][q];
-          if (p.ep_leaky) e[q] = fmaxf(e[q], 0.1f * e[q]);
-        }
-      }
-      if (st_ok && o < p.Cout) {
-        float *dst = obase + (size_t)o * oplane + (size_t)oy * W + ox;
-        if (ox + 3 < W) {
-          mfn_store4_stream(dst, e[0], e[1], e[2], e[3], p.st_policy);
-        } else {
-          MFN_UNROLL
-          for (int q = 0; q < 4; ++q)
-            if (ox + q < W) dst[q] = e[q];
-        }
+      MFN_WAIT_LGKM0();   // the previous tile's reads are done (wave-private buffer: no barrier needed)
+      MFN_UNROLL
+      for (int r = 0; r < 16; ++r) tr[((r & 3) + 8 * (r >> 2) + 4 * kb) * TS + j] = fin[mt][r];
+      MFN_WAIT_LGKM0();
+      MFN_UNROLL
+      for (int i = 0; i < 4; ++i) {
+        const int ol = i * 8 + orow;
+        const float4 v = *reinterpret_cast<const float4 *>(tr + ol * TS + px0);
+        finish_row(m0 + mt * 32 + ol, v, bq[i], addv[i], true);
       }
     }
   }

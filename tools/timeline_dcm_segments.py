@@ -37,7 +37,7 @@ for l in (5, 4, 3, 2):
         print("  tier %d: %4d blocks | setup %.2f | loop med %.2f p90 %.2f max %.2f | epilogue %.2f | end med %.2f max %.2f" % (
             md, q.sum(), np.median(t[q, 1] - t[q, 0]), np.median(t[q, 2] - t[q, 1]), np.percentile(t[q, 2] - t[q, 1], 90), (t[q, 2] - t[q, 1]).max(),
             np.median(t[q, 3] - t[q, 2]), np.median(t[q, 3]), t[q, 3].max()))
-        names = ["offsets", "geometry", "window box", "prologue issue", "first operand", "(loop: stamp 1..2)", "K-slice reduce", "epilogue"]
         seq = [t[q, 0], t2[q, 0], t2[q, 1], t2[q, 2], t2[q, 3], t2[q, 4], t[q, 1], t[q, 2], t2[q, 6], t[q, 3]]
-        lab = ["offsets", "geometry", "window box", "prologue issue", "first operand", "first barrier", "LOOP", "K-slice reduce", "epilogue"]
+        # stamp 6 sits behind the barrier at which the K slices have handed their partial tiles over: the sums are part of the epilogue
+        lab = ["offsets", "geometry", "window box", "prologue issue", "first operand", "first barrier", "LOOP", "K-slice hand-over", "sum + epilogue"]
         print("          " + "  ".join("%s %.2f" % (lab[i], np.median(seq[i + 1] - seq[i])) for i in range(len(lab))))
