@@ -334,6 +334,36 @@ int mfn_augment_color(const float *img1, const float *img2, const float *table, 
                       int W, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The multiscale training loss, fused -- replaces EpeLossWithMask and MultiscaleEpe(match='upsampling') of
+ * /root/reference/network/MaskFlownet.py:563-611 as /root/reference/network/pipeline.py:42-44 builds them (eps 1e-8, q from
+ * optimizer.q: None for the chairs / things schedules, 0.4 for Sintel and KITTI) and :82 calls them.  Per scale s of n_scales,
+ * with factor f_s, weight w_s and prediction p_s (N,2,H/f_s,W/f_s):
+ *   d = Upsample(f_s)(p_s) - label;   L = sqrt(d_y^2 + d_x^2 + eps),  or (|d_y| + |d_x| + eps)^q with robust != 0;
+ *   sums[n,s] = sum_pix mask[n,pix] * L;   sums[n,n_scales] = msum[n] = sum mask[n];   loss[n] = sum_s w_s * sums[n,s] / msum[n].
+ * label: (N,2,H,W); mask: (N,1,H,W), or with mask_is_scalar != 0 (N,1,1,1): msum[n] = mask[n], the numerator over all pixels (the
+ * reference's broadcast).  msum == 0 gives that sample the reference's 0 / 0.  The upsampled value is recomputed per pixel with
+ * mfn_upsample_fwd's own arithmetic (its bits) and never stored; kernels/loss.h spells out every expression (fp contraction off).
+ * preds, factors, weights (and gpreds, reqs) are HOST arrays of n_scales <= MFN_LOSS_MAX_SCALES entries, copied by value into
+ * the launches: no allocation, no synchronisation, capturable.  Fixed-order reductions through the caller's workspace, no
+ * atomics: bit-identical from run to run, |sum - exact| <= 64 * 2^-24 * sum |terms|.
+ * Errors before any launch: n_scales outside 1..8, a factor < 1, q <= 0 with robust (MFN_E_PARAM); H or W no multiple of a
+ * factor (MFN_E_SHAPE); a NULL array or tensor (MFN_E_NULL); a missing or short workspace (MFN_E_WORKSPACE). */
+#define MFN_LOSS_MAX_SCALES 8
+size_t mfn_multiscale_epe_workspace_bytes(int N, int H, int W, int n_scales);
+int mfn_multiscale_epe_fwd(const float *const *preds, const int *factors, const float *weights, int n_scales,
+                           const float *label, const float *mask, int mask_is_scalar, float eps, int robust, float q,
+                           float *loss, float *sums, int N, int H, int W, void *workspace, size_t workspace_bytes, void *stream);
+/* Gradients of the predictions (none of label or mask): gpreds[s] (N,2,H/f_s,W/f_s) =
+ *   gloss[n] * w_s / msum[n] * sum over the (2 f_s - 1)^2 footprint of k_y k_x * mask * dL/dd_c,
+ * dL/dd_c = d_c / sqrt(..), or q * (..)^(q-1) * sign(d_c) with sign(0) = 0; d recomputed from preds and label, msum read from
+ * the forward's sums (N, n_scales + 1).  reqs[s]: MFN_REQ_* per prediction (MFN_REQ_NULL: gpreds[s] may be NULL and is not
+ * touched).  One launch per scale, owner computes, no atomics: bit-identical from run to run.  Pixels with mask == 0 add no
+ * term: an input pixel whose whole footprint is masked out gets exactly 0. */
+int mfn_multiscale_epe_bwd(const float *gloss, const float *const *preds, const int *factors, const float *weights, int n_scales,
+                           const float *label, const float *mask, int mask_is_scalar, float eps, int robust, float q,
+                           const float *sums, float *const *gpreds, const int *reqs, int N, int H, int W, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Convolution / Deconvolution -- replace the Gluon blocks of
  * /root/reference/network/MaskFlownet.py:79-163: nn.Conv2D(channels, kernel_size=3, strides, padding, dilation)
  * [+ LeakyReLU(0.1)] of conv() / predict_flow() / predict_mask() (:165-191) and nn.Conv2DTranspose(channels, 4, 2, 1)

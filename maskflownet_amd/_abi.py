@@ -61,6 +61,12 @@ SIGNATURES = {
     "augment_color_mean_workspace_bytes": (C.c_size_t, [_i] * 3),
     "augment_color_mean": (_i, [_f, _f, _f, C.c_float, C.c_ulonglong, C.c_ulonglong, _f] + [_i] * 3 + [C.c_void_p, C.c_size_t, _s]),
     "augment_color": (_i, [_f, _f, _f, _f, C.c_float, C.c_ulonglong, C.c_ulonglong, _i, _i, _f] + [_i] * 3 + [_s]),
+    # the fused multiscale training loss (kernels/loss.h); host arrays of pointers / ints / floats
+    "multiscale_epe_workspace_bytes": (C.c_size_t, [_i] * 4),
+    "multiscale_epe_fwd": (_i, [C.POINTER(C.c_void_p), _pi, C.POINTER(C.c_float), _i, _f, _f, _i, C.c_float, _i, C.c_float, _f, _f]
+                           + [_i] * 3 + [C.c_void_p, C.c_size_t, _s]),
+    "multiscale_epe_bwd": (_i, [_f, C.POINTER(C.c_void_p), _pi, C.POINTER(C.c_float), _i, _f, _f, _i, C.c_float, _i, C.c_float, _f,
+                                C.POINTER(C.c_void_p), _pi] + [_i] * 3 + [_s]),
     "set_arithmetic": (_i, [C.c_char_p, _i]),
     "get_arithmetic": (_i, [C.c_char_p, _pi]),
     "set_tuning": (_i, [C.c_char_p, _i]),

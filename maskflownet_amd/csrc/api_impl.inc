@@ -20,6 +20,7 @@
 #include "kernels/upsample.h"
 #include "kernels/predict.h"
 #include "kernels/augment.h"
+#include "kernels/loss.h"
 #include "kernels/backward.h"
 #include "kernels/dc_backward.h"
 #include "kernels/conv.h"
@@ -1767,6 +1768,76 @@ int MFN_API(upsample_bwd)(const float *gout, float *gx, int N, int C, int H, int
                           (hipStream_t)stream, p), "upsample_bwd");
   return hipfail(launch("upsample_bwd", upsample_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p),
                  "upsample_bwd");
+}
+
+// ---- the fused multiscale training loss (kernels/loss.h) --------------------------------------------------------------------
+// what both directions accept; the host arrays are read here and travel to the kernels by value
+static int loss_dims(const char *what, const float *const *preds, const int *factors, const float *weights, int n_scales, int N, int H,
+                     int W, int robust, float q) {
+  if (n_scales < 1 || n_scales > MFN_LOSS_MAX_SCALES)
+    return fail(MFN_E_PARAM, "%s: n_scales=%d must be in 1..%d", what, n_scales, MFN_LOSS_MAX_SCALES);
+  if (!preds || !factors || !weights) return fail(MFN_E_NULL, "%s: NULL host array (preds, factors, weights)", what);
+  if (N < 0 || H <= 0 || W <= 0) return fail(MFN_E_SHAPE, "%s: N=%d H=%d W=%d", what, N, H, W);
+  for (int s = 0; s < n_scales; ++s) {
+    if (factors[s] < 1) return fail(MFN_E_PARAM, "%s: factor %d of scale %d must be >= 1", what, factors[s], s);
+    if (factors[s] > LOSS_MAX_FACTOR) return fail(MFN_E_UNSUPPORTED, "%s: factor %d of scale %d is above %d", what, factors[s], s, LOSS_MAX_FACTOR);
+    if (H % factors[s] || W % factors[s])
+      return fail(MFN_E_SHAPE, "%s: H=%d W=%d is no multiple of the factor %d of scale %d", what, H, W, factors[s], s);
+  }
+  if (robust && !(q > 0.f)) return fail(MFN_E_PARAM, "%s: the robust form needs q > 0 (got %g)", what, (double)q);
+  if (N > 65535 || (size_t)H * W > (size_t)LOSS_SLICE * LOSS_MAX_SLICES) return fail(MFN_E_UNSUPPORTED, "%s: tensor too large", what);
+  return 0;
+}
+
+size_t MFN_API(multiscale_epe_workspace_bytes)(int N, int H, int W, int n_scales) {
+  if (N <= 0 || H <= 0 || W <= 0 || n_scales < 1 || n_scales > MFN_LOSS_MAX_SCALES) return 0;
+  return (size_t)N * loss_slices((size_t)H * W) * (n_scales + 1) * sizeof(float);
+}
+
+int MFN_API(multiscale_epe_fwd)(const float *const *preds, const int *factors, const float *weights, int n_scales, const float *label,
+                                const float *mask, int mask_is_scalar, float eps, int robust, float q, float *loss, float *sums, int N,
+                                int H, int W, void *workspace, size_t workspace_bytes, void *stream) {
+  if (int rc = loss_dims("multiscale_epe_fwd", preds, factors, weights, n_scales, N, H, W, robust, q)) return rc;
+  if (N == 0) return 0;
+  if (!label || !mask || !loss || !sums) return fail(MFN_E_NULL, "multiscale_epe_fwd: NULL tensor pointer");
+  for (int s = 0; s < n_scales; ++s)
+    if (!preds[s]) return fail(MFN_E_NULL, "multiscale_epe_fwd: prediction %d is NULL", s);
+  const int slices = loss_slices((size_t)H * W);
+  const size_t need = (size_t)N * slices * (n_scales + 1) * sizeof(float);
+  if (!workspace || workspace_bytes < need)
+    return fail(MFN_E_WORKSPACE, "multiscale_epe_fwd: workspace of %zu bytes needed, %zu given", need, workspace ? workspace_bytes : (size_t)0);
+  if (!aligned(workspace, 4)) return fail(MFN_E_ALIGN, "multiscale_epe_fwd: workspace must be 4-byte aligned");
+  LossFwdParams p{};
+  for (int s = 0; s < n_scales; ++s) { p.pred[s] = preds[s]; p.f[s] = factors[s]; p.magic[s] = mfn_make_magic((unsigned)factors[s]); p.w[s] = weights[s]; }
+  p.S = n_scales; p.label = label; p.mask = mask; p.partial = (float *)workspace; p.sums = sums; p.loss = loss;
+  p.N = N; p.H = H; p.W = W; p.slices = slices; p.mask_scalar = mask_is_scalar ? 1 : 0; p.robust = robust ? 1 : 0;
+  p.eps = eps; p.q = q;
+  return hipfail(multiscale_epe_fwd_launch(p, (hipStream_t)stream), "multiscale_epe_fwd");
+}
+
+int MFN_API(multiscale_epe_bwd)(const float *gloss, const float *const *preds, const int *factors, const float *weights, int n_scales,
+                                const float *label, const float *mask, int mask_is_scalar, float eps, int robust, float q,
+                                const float *sums, float *const *gpreds, const int *reqs, int N, int H, int W, void *stream) {
+  if (int rc = loss_dims("multiscale_epe_bwd", preds, factors, weights, n_scales, N, H, W, robust, q)) return rc;
+  if (!gpreds || !reqs) return fail(MFN_E_NULL, "multiscale_epe_bwd: NULL host array (gpreds, reqs)");
+  bool any = false;
+  for (int s = 0; s < n_scales; ++s) {
+    if (!req_ok(reqs[s])) return fail(MFN_E_PARAM, "multiscale_epe_bwd: req of scale %d must be 0 (null), 1 (write) or 3 (add)", s);
+    if (N != 0 && reqs[s] && (!preds[s] || !gpreds[s])) return fail(MFN_E_NULL, "multiscale_epe_bwd: prediction %d or its gradient is NULL", s);
+    any = any || reqs[s];
+  }
+  if (N == 0 || !any) return 0;
+  if (!gloss || !label || !mask || !sums) return fail(MFN_E_NULL, "multiscale_epe_bwd: NULL tensor pointer");
+  for (int s = 0; s < n_scales; ++s) {
+    if (!reqs[s]) continue;
+    LossBwdParams p{};
+    p.pred = preds[s]; p.gpred = gpreds[s]; p.f = factors[s]; p.magic = mfn_make_magic((unsigned)factors[s]); p.add = reqs[s] == MFN_REQ_ADD ? 1 : 0; p.w = weights[s];
+    p.label = label; p.mask = mask; p.gloss = gloss; p.sums = sums; p.S1 = n_scales + 1;
+    p.N = N; p.H = H; p.W = W; p.h = H / factors[s]; p.wd = W / factors[s];
+    p.mask_scalar = mask_is_scalar ? 1 : 0; p.robust = robust ? 1 : 0; p.eps = eps; p.q = q;
+    if (int rc = hipfail(multiscale_epe_bwd_launch(p, (hipStream_t)stream), "multiscale_epe_bwd")) return rc;
+  }
+  return 0;
 }
 
 int MFN_API(leaky_relu_bwd)(const float *gout, const float *y, float *gin, size_t n, float slope, void *stream) {

@@ -27,10 +27,61 @@ __device__ __forceinline__ float upsample_tri(int cc, int a) {
   return 1.f - fabsf((float)(cc - a)) / (float)(cc + 1);  // the reference's _kernel2d entry, same rounding
 }
 
+// One output pixel, in three steps that upsample_kernel and the fused multiscale loss (loss.h) share: the loss recomputes
+// Upsample(f)(p) per pixel and has to get upsample_kernel's bits (its gradient is discontinuous where the difference to the
+// label changes sign), so the arithmetic lives here once.  `tri(a)` supplies upsample_tri(f - 1, a) -- computed on the spot
+// here, read from a table of exactly those values in loss.h -- and `div(o)` is o / f (a plain or a multiply-shift division:
+// integers, exact either way).  Row part: the two input rows and their weights.
+struct UpsampleRow { size_t o0, o1; float ka0, ka1; int i0, i1, ry; };
+template <class Tri, class Div>
+__device__ __forceinline__ UpsampleRow upsample_row(int H, int W, int f, int oy, Tri tri, Div div) {
+  UpsampleRow r;
+  r.i0 = div(oy);
+  r.ry = oy - r.i0 * f;
+  r.i1 = min(r.i0 + 1, H - 1);
+  r.ka0 = tri(r.ry + f - 1);                  // row iy0
+  r.ka1 = r.ry ? tri(r.ry - 1) : 0.f;         // row iy0 + 1 (absent when r == 0)
+  r.o0 = (size_t)r.i0 * W;
+  r.o1 = (size_t)r.i1 * W;
+  return r;
+}
+// Column part: the two input columns and their weights.
+struct UpsampleCol { int ix0, ix1; float kb0, kb1; int rx; };
+template <class Tri, class Div>
+__device__ __forceinline__ UpsampleCol upsample_col(int W, int f, int ox, Tri tri, Div div) {
+  UpsampleCol c;
+  c.ix0 = div(ox);
+  c.rx = ox - c.ix0 * f;
+  c.ix1 = min(c.ix0 + 1, W - 1);
+  c.kb0 = tri(c.rx + f - 1);
+  c.kb1 = c.rx ? tri(c.rx - 1) : 0.f;
+  return c;
+}
+// The blend: dst += v * (ka * kb) in raster order of the contributing inputs; no contraction into FMAs.  `ld(rs, cs)` supplies the
+// input at (row rs ? i1 : i0, column cs ? ix1 : ix0) -- from the plane in global memory here, from a staged patch in loss.h.
+template <class Ld>
+__device__ __forceinline__ float upsample_blend(Ld ld, const UpsampleRow &r, const UpsampleCol &c) {
+#pragma clang fp contract(off)
+  float acc = ld(0, 0) * (r.ka0 * c.kb0);
+  if (c.rx) acc = acc + ld(0, 1) * (r.ka0 * c.kb1);
+  if (r.ry) {
+    acc = acc + ld(1, 0) * (r.ka1 * c.kb0);
+    if (c.rx) acc = acc + ld(1, 1) * (r.ka1 * c.kb1);
+  }
+  return acc;
+}
+// ld of a plane in global memory
+struct UpsamplePlane {
+  const float *src;
+  const UpsampleRow &r;
+  const UpsampleCol &c;
+  __device__ __forceinline__ float operator()(int rs, int cs) const { return src[(rs ? r.o1 : r.o0) + (cs ? c.ix1 : c.ix0)]; }
+};
+
 template <int VEC>
 __global__ __launch_bounds__(256) void upsample_kernel(UpsampleParams p) {
 #pragma clang fp contract(off)
-  const int f = p.f, cc = f - 1;
+  const int f = p.f;
   const int Hout = p.H * f, Wout = p.W * f;
   const int wv = Wout / VEC;
   const size_t total = (size_t)p.N * p.C * Hout * wv;
@@ -40,27 +91,14 @@ __global__ __launch_bounds__(256) void upsample_kernel(UpsampleParams p) {
   const int oy = (int)((idx / wv) % Hout);
   const size_t nc = idx / ((size_t)wv * Hout);
   const float *src = p.x + nc * (size_t)p.H * p.W;
-  const int iy0 = oy / f, ry = oy - iy0 * f;
-  const float ka0 = upsample_tri(cc, ry + f - 1);               // row iy0
-  const float ka1 = ry ? upsample_tri(cc, ry - 1) : 0.f;        // row iy0 + 1 (absent when r == 0)
-  const float *r0 = src + (size_t)iy0 * p.W;
-  const float *r1 = src + (size_t)min(iy0 + 1, p.H - 1) * p.W;
+  auto tri = [f](int a) { return upsample_tri(f - 1, a); };
+  auto div = [f](int o) { return o / f; };
+  const UpsampleRow row = upsample_row(p.H, p.W, f, oy, tri, div);
   float o[VEC];
   MFN_UNROLL
   for (int k = 0; k < VEC; ++k) {
-    const int ox = xv * VEC + k;
-    const int ix0 = ox / f, rx = ox - ix0 * f;
-    const int ix1 = min(ix0 + 1, p.W - 1);
-    const float kb0 = upsample_tri(cc, rx + f - 1);
-    const float kb1 = rx ? upsample_tri(cc, rx - 1) : 0.f;
-    // dst += v * (ka * kb) in raster order of the contributing inputs; no contraction into FMAs
-    float acc = r0[ix0] * (ka0 * kb0);
-    if (rx) acc = acc + r0[ix1] * (ka0 * kb1);
-    if (ry) {
-      acc = acc + r1[ix0] * (ka1 * kb0);
-      if (rx) acc = acc + r1[ix1] * (ka1 * kb1);
-    }
-    o[k] = acc;
+    const UpsampleCol col = upsample_col(p.W, f, xv * VEC + k, tri, div);
+    o[k] = upsample_blend(UpsamplePlane{src, row, col}, row, col);
   }
   float *dst = p.out + nc * (size_t)Hout * Wout + (size_t)oy * Wout + (size_t)xv * VEC;
   if (VEC == 4) {

@@ -589,6 +589,72 @@ class OpSet:
                                          self.ad.ptr(out), N, H, W, self.ad.stream(a)))
         return out
 
+    # ---- the fused multiscale training loss (MaskFlownet.py:563-611 as pipeline.py:42-44 builds it) --------------------------------
+    def _loss_args(self, what, preds, label, mask, scales, weights, q):
+        preds = self._in(*preds)
+        l, m = self._in(label, mask)
+        scales, weights = [int(f) for f in scales], [float(w) for w in weights]
+        S = len(preds)
+        if not 1 <= S <= 8 or len(scales) != S or len(weights) != S:
+            raise ValueError("%s: 1..8 predictions with one scale and one weight each, got %d predictions, %d scales, %d weights"
+                             % (what, S, len(scales), len(weights)))
+        if self.ad.ndim(l) != 4 or self.ad.shape(l)[1] != 2:
+            raise ValueError("%s: label must be (N,2,H,W), got %s" % (what, self.ad.shape(l)))
+        N, _, H, W = self.ad.shape(l)
+        if self.ad.shape(m) not in ((N, 1, H, W), (N, 1, 1, 1)):
+            raise ValueError("%s: mask must have shape %s or %s, got %s" % (what, (N, 1, H, W), (N, 1, 1, 1), self.ad.shape(m)))
+        for p, f in zip(preds, scales):
+            if f < 1 or H % f or W % f or self.ad.shape(p) != (N, 2, H // f, W // f):
+                raise ValueError("%s: the prediction of scale %d must have shape (N,2,H/%d,W/%d) of label %s, got %s"
+                                 % (what, f, f, f, self.ad.shape(l), self.ad.shape(p)))
+        if q is not None and not float(q) > 0:
+            raise ValueError("%s: q must be positive (or None for the sqrt form), got %r" % (what, q))
+        scalar = int(self.ad.shape(m) != (N, 1, H, W))
+        host = ((ctypes.c_void_p * S)(*[self.ad.ptr(p) for p in preds]), (ctypes.c_int * S)(*scales), (ctypes.c_float * S)(*weights))
+        return preds, l, m, scales, host, scalar, (N, H, W)
+
+    def multiscale_epe(self, preds, label, mask, scales, weights, eps=1e-8, q=None):
+        """MultiscaleEpe(scales, weights, match='upsampling', eps, q) of MaskFlownet.py:585-611 in two launches: preds[s]
+        (N,2,H/scales[s],W/scales[s]), label (N,2,H,W), mask (N,1,H,W) or (N,1,1,1) -> (loss (N,), sums (N,S+1): the S masked sums
+        and sum(mask)).  q=None: sqrt(dy^2 + dx^2 + eps); q: (|dy| + |dx| + eps)^q.  No full-resolution tensor is written."""
+        preds, l, m, scales, (pp, ff, ww), scalar, (N, H, W) = self._loss_args("multiscale_epe", preds, label, mask, scales, weights, q)
+        S = len(preds)
+        loss = self.ad.empty(l, (N,))
+        sums = self.ad.empty(l, (N, S + 1))
+        ws = self._workspace(l, self.ns.multiscale_epe_workspace_bytes(N, H, W, S))
+        self.check(self.ns.multiscale_epe_fwd(pp, ff, ww, S, self.ad.ptr(l), self.ad.ptr(m), scalar, float(eps), int(q is not None),
+                                              float(q or 0.0), self.ad.ptr(loss), self.ad.ptr(sums), N, H, W, self.ad.ptr(ws),
+                                              self.ad.nbytes(ws), self.ad.stream(l)))
+        return loss, sums
+
+    def multiscale_epe_backward(self, gloss, preds, label, mask, scales, weights, sums, eps=1e-8, q=None, reqs=None, out=None):
+        """Gradients of multiscale_epe's loss with respect to the predictions: gloss (N,), sums as the forward returned them ->
+        a tuple with one (N,2,h,w) gradient per prediction (None where req is 'null').  reqs: 'write' / 'add' / 'null' per
+        prediction (default all 'write'); out: the destinations ('add' needs them)."""
+        what = "multiscale_epe_backward"
+        preds, l, m, scales, (pp, ff, ww), scalar, (N, H, W) = self._loss_args(what, preds, label, mask, scales, weights, q)
+        S = len(preds)
+        g, sm = self._in(gloss, sums)
+        if self.ad.shape(g) != (N,) or self.ad.shape(sm) != (N, S + 1):
+            raise ValueError("%s: gloss must be %s and sums %s, got %s and %s" % (what, (N,), (N, S + 1), self.ad.shape(g), self.ad.shape(sm)))
+        reqs = ["write"] * S if reqs is None else list(reqs)
+        out = [None] * S if out is None else list(out)
+        if len(reqs) != S or len(out) != S:
+            raise ValueError("%s: reqs and out must have one entry per prediction" % what)
+        gp = []
+        for s in range(S):
+            if _REQ[reqs[s]] == 0:
+                gp.append(None)
+                continue
+            if _REQ[reqs[s]] == _REQ["add"] and out[s] is None:
+                raise ValueError("%s: req 'add' needs the buffer to add into" % what)
+            gp.append(self._out(out[s], l, self.ad.shape(preds[s]), what))
+        gptr = (ctypes.c_void_p * S)(*[None if t is None else self.ad.ptr(t) for t in gp])
+        rr = (ctypes.c_int * S)(*[_REQ[r] for r in reqs])
+        self.check(self.ns.multiscale_epe_bwd(self.ad.ptr(g), pp, ff, ww, S, self.ad.ptr(l), self.ad.ptr(m), scalar, float(eps),
+                                              int(q is not None), float(q or 0.0), self.ad.ptr(sm), gptr, rr, N, H, W, self.ad.stream(l)))
+        return tuple(gp)
+
     def Upsample_backward(self, out_grad, factor, req="write", out=None):
         """Adjoint of Upsample(factor): (N,C,H*f,W*f) -> (N,C,H,W) (mfn_upsample_bwd)."""
         (go,) = self._in(out_grad)
@@ -989,6 +1055,14 @@ def augment_color_mean(*a, **k):
 
 def augment_color(*a, **k):
     return default_ops().augment_color(*a, **k)
+
+
+def multiscale_epe(*a, **k):
+    return default_ops().multiscale_epe(*a, **k)
+
+
+def multiscale_epe_backward(*a, **k):
+    return default_ops().multiscale_epe_backward(*a, **k)
 
 
 def Convolution(*a, **k):

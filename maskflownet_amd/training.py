@@ -216,20 +216,62 @@ class MaskFlownetTrainable(nn.Module):
 
 class MultiscaleEpe(nn.Module):
     """MaskFlownet.py:585-611 with match='upsampling' (pipeline.py:42-44): sum_s w_s * EpeLossWithMask(Upsample(s)(pred_s) ,
-    label, mask); EpeLossWithMask (:563-583) = sum(sqrt(sum_c (p - l)^2 + eps) * mask) / sum(mask) per sample.
-    `label` in pixels, as the predictions (flow x scale)."""
+    label, mask); EpeLossWithMask (:563-583) = sum(sqrt(sum_c (p - l)^2 + eps) * mask) / sum(mask) per sample, or with q (the
+    `optimizer.q` of the Sintel / KITTI schedules, :577-578) sum((sum_c |p - l| + eps)^q * mask) / sum(mask).
+    `label` in pixels, as the predictions (flow x scale).  Composed from Upsample and torch element-wise kernels: the torch twin
+    of FusedMultiscaleEpe."""
 
-    def __init__(self, scales=(64, 32, 16, 8, 4), weights=(.005, .01, .02, .08, .32), eps=1e-8, backend=None):
+    def __init__(self, scales=(64, 32, 16, 8, 4), weights=(.005, .01, .02, .08, .32), eps=1e-8, backend=None, q=None):
         super().__init__()
         self.scales, self.weights, self.eps = tuple(scales), tuple(weights), float(eps)
+        self.q = None if q is None else float(q)
         self.B = backend if backend is not None else LibraryBackend()
 
     def forward(self, label, mask, *preds):
         total = 0.
         for p, w, s in zip(preds, self.weights, self.scales):
-            e = torch.sqrt(((self.B.upsample(p, s) - label) ** 2).sum(1) + self.eps) * mask[:, 0]
+            if self.q is None:
+                e = torch.sqrt(((self.B.upsample(p, s) - label) ** 2).sum(1) + self.eps) * mask[:, 0]
+            else:
+                e = ((self.B.upsample(p, s) - label).abs().sum(1) + self.eps) ** self.q * mask[:, 0]
             total = total + w * e.flatten(1).sum(1) / mask.flatten(1).sum(1)
         return total
+
+
+class _FusedEpeFn(torch.autograd.Function):
+    """mfn_multiscale_epe_fwd / _bwd: nothing but the predictions, label, mask and the (N, S+1) sums is kept for backward."""
+
+    @staticmethod
+    def forward(ctx, label, mask, cfg, *preds):
+        scales, weights, eps, q = cfg
+        preds = tuple(p.contiguous() for p in preds)
+        loss, sums = ops.multiscale_epe(preds, label, mask, scales, weights, eps, q)
+        ctx.save_for_backward(label, mask, sums, *preds)
+        ctx.cfg = cfg
+        return loss
+
+    @staticmethod
+    def backward(ctx, gloss):
+        label, mask, sums, *preds = ctx.saved_tensors
+        scales, weights, eps, q = ctx.cfg
+        reqs = ["write" if need else "null" for need in ctx.needs_input_grad[3:]]
+        gp = ops.multiscale_epe_backward(gloss.contiguous(), preds, label, mask, scales, weights, sums, eps, q, reqs=reqs)
+        return (None, None, None) + tuple(gp)
+
+
+class FusedMultiscaleEpe(nn.Module):
+    """MultiscaleEpe on the library's fused kernels (kernels/loss.h): the same defaults, call `(label, mask, *preds)`, per-sample
+    return value and `.scales`; forward is two launches, backward one per scale, and no full-resolution tensor is written or kept.
+    q=None: the sqrt form; q (0.4 in the Sintel / KITTI schedules): the robust form.  Gradients reach the predictions only."""
+
+    def __init__(self, scales=(64, 32, 16, 8, 4), weights=(.005, .01, .02, .08, .32), eps=1e-8, q=None):
+        super().__init__()
+        self.scales, self.weights, self.eps = tuple(scales), tuple(weights), float(eps)
+        self.q = None if q is None else float(q)
+
+    def forward(self, label, mask, *preds):
+        n = len(preds)
+        return _FusedEpeFn.apply(label, mask, (self.scales[:n], self.weights[:n], self.eps, self.q), *preds)
 
 
 class GradientBuckets:

@@ -45,6 +45,9 @@
 #define mfn_bilinear_resize_fwd mfn_emu_bilinear_resize_fwd
 #define mfn_flow_metrics_workspace_bytes mfn_emu_flow_metrics_workspace_bytes
 #define mfn_flow_metrics mfn_emu_flow_metrics
+#define mfn_multiscale_epe_workspace_bytes mfn_emu_multiscale_epe_workspace_bytes
+#define mfn_multiscale_epe_fwd mfn_emu_multiscale_epe_fwd
+#define mfn_multiscale_epe_bwd mfn_emu_multiscale_epe_bwd
 #define mfn_conv2d_out_shape mfn_emu_conv2d_out_shape
 #define mfn_conv2d_workspace_bytes mfn_emu_conv2d_workspace_bytes
 #define mfn_conv2d_packed_weight_bytes mfn_emu_conv2d_packed_weight_bytes
@@ -272,6 +275,29 @@ static void others() {
     const size_t need2 = mfn_flow_metrics_workspace_bytes(N, H, W);
     Block ws2(need2);
     report("flow_metrics", mfn_flow_metrics(fl.f(), lab.f(), mask.f(), sums.f(), N, H, W, ws2.p, need2, nullptr));
+  }
+  // the fused multiscale loss: forward v4 / v1, backward with 1, 64 and 256 threads per input pixel, plane and per-sample mask, both forms
+  struct LossRow { const char *name; int N, h, w, f0, f1, scalar_mask, robust; };
+  for (const LossRow &r : {LossRow{"multiscale_epe v4, t1 + t64", 2, 2, 4, 4, 8, 0, 0}, LossRow{"multiscale_epe v1, t1 (f = 3, 1)", 2, 3, 5, 3, 1, 0, 1},
+                           LossRow{"multiscale_epe v4, t256 + t64, scalar mask", 1, 1, 2, 32, 16, 1, 1}, LossRow{"multiscale_epe W = 1", 1, 3, 1, 1, 1, 1, 0}}) {
+    const int H = r.h * r.f0, W = r.w * r.f0, fs[2] = {r.f0, r.f1};
+    Tensor p0((size_t)r.N * 2 * r.h * r.w, 4.f), p1((size_t)r.N * 2 * (H / r.f1) * (W / r.f1), 4.f), lab((size_t)r.N * 2 * H * W, 4.f);
+    Tensor mask(r.scalar_mask ? (size_t)r.N : (size_t)r.N * H * W), loss(r.N, 1.f, false), sums(r.N * 3, 1.f, false), gloss(r.N);
+    Tensor g0(p0.n, 1.f, false), g1(p1.n);
+    for (size_t i = 0; i < mask.n; ++i) mask.f()[i] = mask.f()[i] > 0.4f ? 0.f : 1.f;
+    const float *preds[2] = {p0.f(), p1.f()};
+    float *gp[2] = {g0.f(), g1.f()};
+    const float wts[2] = {0.32f, 0.08f};
+    const int reqs[2] = {MFN_REQ_WRITE, MFN_REQ_ADD};
+    const size_t need = mfn_multiscale_epe_workspace_bytes(r.N, H, W, 2);
+    Block ws(need);
+    char name[96];
+    snprintf(name, sizeof(name), "%s fwd", r.name);
+    report(name, mfn_multiscale_epe_fwd(preds, fs, wts, 2, lab.f(), mask.f(), r.scalar_mask, 1e-8f, r.robust, 0.4f, loss.f(), sums.f(), r.N, H, W, ws.p,
+                                        need, nullptr));
+    snprintf(name, sizeof(name), "%s bwd", r.name);
+    report(name, mfn_multiscale_epe_bwd(gloss.f(), preds, fs, wts, 2, lab.f(), mask.f(), r.scalar_mask, 1e-8f, r.robust, 0.4f, sums.f(), gp, reqs, r.N, H,
+                                        W, nullptr));
   }
 }
 
