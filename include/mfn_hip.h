@@ -364,6 +364,36 @@ int mfn_multiscale_epe_bwd(const float *gloss, const float *const *preds, const 
                            const float *sums, float *const *gpreds, const int *reqs, int N, int H, int W, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The trainer's Adam step -- replaces `self.trainer.step(batch_size)` of /root/reference/network/pipeline.py:114
+ * for the trainer of :27, gluon.Trainer(params, 'adam', {'learning_rate': 1e-4}).  mfn_adam_update is MXNet 1.5's `adam_update`
+ * operator (src/operator/optimizer_op-inl.h, AdamUpdate) with its own signature, in place on n fp32 elements:
+ *   g  = rescale_grad * grad + wd * weight;   g = clip_gradient >= 0 ? clip(g, -clip_gradient, clip_gradient) : g;
+ *   mean = beta1 * mean + (1 - beta1) * g;    var = beta2 * var + (1 - beta2) * g * g;
+ *   weight = weight - lr * mean / (sqrt(var) + epsilon)
+ * kernels/optimizer.h spells out the evaluation order (every operation rounded in fp32, fp contraction off).  The bias corrections
+ * are the caller's, folded into lr as MXNet's Adam.update does: lr * sqrt(1 - beta2^t) / (1 - beta1^t).  NaN and inf propagate per
+ * element.  Every element is owned by one thread: no atomics, no workspace, bit-identical from run to run.
+ * Errors before any launch: n < 0 (MFN_E_SHAPE); a NULL pointer with n > 0 (MFN_E_NULL); beta1 or beta2 outside [0, 1),
+ * epsilon < 0 (MFN_E_PARAM); a pointer that is not 4-byte aligned (MFN_E_ALIGN).  n == 0 succeeds without a launch. */
+int mfn_adam_update(float *weight, const float *grad, float *mean, float *var, long long n, float lr, float beta1, float beta2,
+                    float epsilon, float wd, float rescale_grad, float clip_gradient, void *stream);
+/* All tensors of a step in ONE launch.  A table says where they are: per tensor the four pointers, the count, lr_mult and wd_mult (the
+ * tensor's lr is lr * lr_mult, its wd wd * wd_mult; NULL arrays mean 1) and whether all four pointers are 16-byte aligned (such
+ * tensors move 16 bytes per access, the others one element), then one entry per block of 4096 elements.  The two host-only entries
+ * size and fill the table in a caller-owned HOST buffer (8-byte aligned) from HOST arrays of DEVICE pointers; the caller uploads the
+ * bytes as they are: the library allocates nothing and synchronises nothing.  mfn_multi_adam_build_table returns the launch's block
+ * count and a layout tag; mfn_multi_adam_update refuses a tag or byte count that does not fit n_tensors and n_blocks
+ * (MFN_E_WORKSPACE).  A tensor whose address or size changed needs a new table.  counts[i] == 0 is allowed (its pointers may be
+ * NULL); a negative count is MFN_E_SHAPE, a NULL pointer of a non-empty tensor MFN_E_NULL.  mfn_multi_adam_table_bytes returns 0
+ * for arguments the builder refuses.  n_tensors == 0 succeeds without a launch. */
+size_t mfn_multi_adam_table_bytes(int n_tensors, const long long *counts);
+int mfn_multi_adam_build_table(int n_tensors, float *const *weights, const float *const *grads, float *const *means,
+                               float *const *vars, const long long *counts, const float *lr_mults, const float *wd_mults,
+                               void *table_host, size_t table_bytes, int *n_blocks, unsigned long long *tag);
+int mfn_multi_adam_update(const void *table_dev, size_t table_bytes, unsigned long long tag, int n_tensors, int n_blocks, float lr,
+                          float beta1, float beta2, float epsilon, float wd, float rescale_grad, float clip_gradient, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Convolution / Deconvolution -- replace the Gluon blocks of
  * /root/reference/network/MaskFlownet.py:79-163: nn.Conv2D(channels, kernel_size=3, strides, padding, dilation)
  * [+ LeakyReLU(0.1)] of conv() / predict_flow() / predict_mask() (:165-191) and nn.Conv2DTranspose(channels, 4, 2, 1)

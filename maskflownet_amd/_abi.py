@@ -67,6 +67,12 @@ SIGNATURES = {
                            + [_i] * 3 + [C.c_void_p, C.c_size_t, _s]),
     "multiscale_epe_bwd": (_i, [_f, C.POINTER(C.c_void_p), _pi, C.POINTER(C.c_float), _i, _f, _f, _i, C.c_float, _i, C.c_float, _f,
                                 C.POINTER(C.c_void_p), _pi] + [_i] * 3 + [_s]),
+    # the trainer's Adam step (kernels/optimizer.h); the table entries are host-only
+    "adam_update": (_i, [_f] * 4 + [C.c_longlong] + [C.c_float] * 7 + [_s]),
+    "multi_adam_table_bytes": (C.c_size_t, [_i, C.POINTER(C.c_longlong)]),
+    "multi_adam_build_table": (_i, [_i] + [C.POINTER(C.c_void_p)] * 4 + [C.POINTER(C.c_longlong), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                        C.c_void_p, C.c_size_t, _pi, C.POINTER(C.c_ulonglong)]),
+    "multi_adam_update": (_i, [C.c_void_p, C.c_size_t, C.c_ulonglong, _i, _i] + [C.c_float] * 7 + [_s]),
     "set_arithmetic": (_i, [C.c_char_p, _i]),
     "get_arithmetic": (_i, [C.c_char_p, _pi]),
     "set_tuning": (_i, [C.c_char_p, _i]),

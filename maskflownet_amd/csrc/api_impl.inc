@@ -21,6 +21,7 @@
 #include "kernels/predict.h"
 #include "kernels/augment.h"
 #include "kernels/loss.h"
+#include "kernels/optimizer.h"
 #include "kernels/backward.h"
 #include "kernels/dc_backward.h"
 #include "kernels/conv.h"
@@ -1838,6 +1839,111 @@ int MFN_API(multiscale_epe_bwd)(const float *gloss, const float *const *preds, c
     if (int rc = hipfail(multiscale_epe_bwd_launch(p, (hipStream_t)stream), "multiscale_epe_bwd")) return rc;
   }
   return 0;
+}
+
+// ---- the trainer's Adam step (kernels/optimizer.h) ---------------------------------------------------------------------------
+// what both forms accept of the operator's scalars
+static int adam_hyper(const char *what, float beta1, float beta2, float epsilon) {
+  if (!(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f))
+    return fail(MFN_E_PARAM, "%s: beta1=%g and beta2=%g must be in [0, 1)", what, (double)beta1, (double)beta2);
+  if (!(epsilon >= 0.f)) return fail(MFN_E_PARAM, "%s: epsilon=%g must be >= 0", what, (double)epsilon);
+  return 0;
+}
+// blocks of a table over these counts, or -1 (a negative count, or more blocks than a launch has)
+static long long adam_count_blocks(int n_tensors, const long long *counts) {
+  unsigned long long nb = 0;
+  for (int i = 0; i < n_tensors; ++i) {
+    if (counts[i] < 0) return -1;
+    nb += adam_blocks_of((unsigned long long)counts[i]);
+    if (nb > 0x7FFFFFFFull) return -1;
+  }
+  return (long long)nb;
+}
+
+int MFN_API(adam_update)(float *weight, const float *grad, float *mean, float *var, long long n, float lr, float beta1, float beta2,
+                         float epsilon, float wd, float rescale_grad, float clip_gradient, void *stream) {
+  if (n < 0) return fail(MFN_E_SHAPE, "adam_update: n=%lld", n);
+  if (int rc = adam_hyper("adam_update", beta1, beta2, epsilon)) return rc;
+  if (n == 0) return 0;
+  if (!weight || !grad || !mean || !var) return fail(MFN_E_NULL, "adam_update: NULL tensor pointer");
+  if (!aligned(weight, 4) || !aligned(grad, 4) || !aligned(mean, 4) || !aligned(var, 4))
+    return fail(MFN_E_ALIGN, "adam_update: pointers must be 4-byte aligned");
+  if (adam_blocks_of((unsigned long long)n) > 0x7FFFFFFFull) return fail(MFN_E_UNSUPPORTED, "adam_update: n=%lld is more than one launch covers", n);
+  AdamTensor t{};
+  t.w = weight; t.g = grad; t.m = mean; t.v = var; t.n = (unsigned long long)n; t.lr_mult = 1.f; t.wd_mult = 1.f;
+  t.aligned16 = adam_aligned16(weight, grad, mean, var) ? 1u : 0u;
+  return hipfail(adam_update_launch(t, AdamHyper{lr, beta1, beta2, epsilon, wd, rescale_grad, clip_gradient}, (hipStream_t)stream), "adam_update");
+}
+
+size_t MFN_API(multi_adam_table_bytes)(int n_tensors, const long long *counts) {
+  if (n_tensors <= 0 || !counts) return 0;
+  const long long nb = adam_count_blocks(n_tensors, counts);
+  return nb < 0 ? 0 : adam_table_bytes((unsigned)n_tensors, (unsigned long long)nb);
+}
+
+int MFN_API(multi_adam_build_table)(int n_tensors, float *const *weights, const float *const *grads, float *const *means,
+                                    float *const *vars, const long long *counts, const float *lr_mults, const float *wd_mults,
+                                    void *table_host, size_t table_bytes, int *n_blocks, unsigned long long *tag) {
+  if (n_tensors < 0) return fail(MFN_E_SHAPE, "multi_adam_build_table: n_tensors=%d", n_tensors);
+  if (!n_blocks || !tag) return fail(MFN_E_NULL, "multi_adam_build_table: NULL output (n_blocks, tag)");
+  if (n_tensors == 0) {
+    *n_blocks = 0;
+    *tag = adam_table_tag(0, 0);
+    return 0;
+  }
+  if (!weights || !grads || !means || !vars || !counts) return fail(MFN_E_NULL, "multi_adam_build_table: NULL host array");
+  const long long nb = adam_count_blocks(n_tensors, counts);
+  if (nb < 0) {
+    for (int i = 0; i < n_tensors; ++i)
+      if (counts[i] < 0) return fail(MFN_E_SHAPE, "multi_adam_build_table: count %lld of tensor %d", counts[i], i);
+    return fail(MFN_E_UNSUPPORTED, "multi_adam_build_table: more blocks than one launch has");
+  }
+  for (int i = 0; i < n_tensors; ++i) {
+    if (counts[i] == 0) continue;
+    if (!weights[i] || !grads[i] || !means[i] || !vars[i]) return fail(MFN_E_NULL, "multi_adam_build_table: tensor %d has a NULL pointer", i);
+    if (!aligned(weights[i], 4) || !aligned(grads[i], 4) || !aligned(means[i], 4) || !aligned(vars[i], 4))
+      return fail(MFN_E_ALIGN, "multi_adam_build_table: the pointers of tensor %d must be 4-byte aligned", i);
+  }
+  const size_t need = adam_table_bytes((unsigned)n_tensors, (unsigned long long)nb);
+  if (!table_host || table_bytes < need)
+    return fail(MFN_E_WORKSPACE, "multi_adam_build_table: a table of %zu bytes needed, %zu given", need, table_host ? table_bytes : (size_t)0);
+  if (!aligned(table_host, 8)) return fail(MFN_E_ALIGN, "multi_adam_build_table: the table must be 8-byte aligned");
+  char *out = (char *)table_host;
+  unsigned block = 0;
+  for (int i = 0; i < n_tensors; ++i) {
+    AdamTensor t{};
+    t.w = weights[i]; t.g = grads[i]; t.m = means[i]; t.v = vars[i]; t.n = (unsigned long long)counts[i];
+    t.lr_mult = lr_mults ? lr_mults[i] : 1.f;
+    t.wd_mult = wd_mults ? wd_mults[i] : 1.f;
+    t.aligned16 = adam_aligned16(weights[i], grads[i], means[i], vars[i]) ? 1u : 0u;
+    t.first_block = block;
+    memcpy(out + (size_t)i * sizeof(AdamTensor), &t, sizeof(t));
+    const unsigned chunks = (unsigned)adam_blocks_of(t.n);
+    for (unsigned c = 0; c < chunks; ++c, ++block) {
+      const AdamBlock b{(unsigned)i, c};
+      memcpy(out + (size_t)n_tensors * sizeof(AdamTensor) + (size_t)block * sizeof(AdamBlock), &b, sizeof(b));
+    }
+  }
+  *n_blocks = (int)nb;
+  *tag = adam_table_tag((unsigned)n_tensors, (unsigned)nb);
+  return 0;
+}
+
+int MFN_API(multi_adam_update)(const void *table_dev, size_t table_bytes, unsigned long long tag, int n_tensors, int n_blocks, float lr,
+                               float beta1, float beta2, float epsilon, float wd, float rescale_grad, float clip_gradient, void *stream) {
+  if (n_tensors < 0 || n_blocks < 0) return fail(MFN_E_SHAPE, "multi_adam_update: n_tensors=%d n_blocks=%d", n_tensors, n_blocks);
+  if (int rc = adam_hyper("multi_adam_update", beta1, beta2, epsilon)) return rc;
+  if (tag != adam_table_tag((unsigned)n_tensors, (unsigned)n_blocks))
+    return fail(MFN_E_WORKSPACE, "multi_adam_update: the table (tag %llx) was not built for %d tensors in %d blocks (tag %llx): "
+                "re-run mfn_multi_adam_build_table", tag, n_tensors, n_blocks, adam_table_tag((unsigned)n_tensors, (unsigned)n_blocks));
+  if (n_tensors == 0 || n_blocks == 0) return 0;
+  const size_t need = adam_table_bytes((unsigned)n_tensors, (unsigned long long)n_blocks);
+  if (!table_dev) return fail(MFN_E_NULL, "multi_adam_update: NULL table");
+  if (table_bytes != need) return fail(MFN_E_WORKSPACE, "multi_adam_update: a table of %zu bytes expected, %zu given", need, table_bytes);
+  if (!aligned(table_dev, 8)) return fail(MFN_E_ALIGN, "multi_adam_update: the table must be 8-byte aligned");
+  return hipfail(multi_adam_update_launch(table_dev, (unsigned)n_tensors, (unsigned)n_blocks,
+                                          AdamHyper{lr, beta1, beta2, epsilon, wd, rescale_grad, clip_gradient}, (hipStream_t)stream),
+                 "multi_adam_update");
 }
 
 int MFN_API(leaky_relu_bwd)(const float *gout, const float *y, float *gin, size_t n, float slope, void *stream) {

@@ -655,6 +655,78 @@ class OpSet:
                                               int(q is not None), float(q or 0.0), self.ad.ptr(sm), gptr, rr, N, H, W, self.ad.stream(l)))
         return tuple(gp)
 
+    # ---- the trainer's Adam step (MXNet's adam_update, pipeline.py:27 and :114) ---------------------------------------------------
+    def _adam_tensors(self, what, weight, grad, mean, var):
+        """The four tensors of one parameter as they are (updated in place: no copy may come between)."""
+        ts = [self.ad.prepare_strided(t) for t in (weight, grad, mean, var)]
+        shape = self.ad.shape(ts[0])
+        n = 1
+        for d in shape:
+            n *= int(d)
+        dense, st = [], 1
+        for d in reversed(shape):
+            dense.insert(0, st)
+            st *= int(d)
+        for name, t in zip(("weight", "grad", "mean", "var"), ts):
+            if self.ad.shape(t) != shape:
+                raise ValueError("%s: %s has shape %s, weight %s" % (what, name, self.ad.shape(t), shape))
+            if n and any(d > 1 and a != b for d, a, b in zip(shape, self.ad.elem_strides(t), dense)):
+                raise ValueError("%s: %s must be contiguous (strides %s)" % (what, name, self.ad.elem_strides(t)))
+        return ts, n
+
+    @staticmethod
+    def _adam_scalars(lr, beta1, beta2, epsilon, wd, rescale_grad, clip_gradient):
+        clip = -1.0 if clip_gradient is None else float(clip_gradient)
+        return (float(lr), float(beta1), float(beta2), float(epsilon), float(wd), float(rescale_grad), clip)
+
+    def adam_update(self, weight, grad, mean, var, lr, beta1=0.9, beta2=0.999, epsilon=1e-8, wd=0.0, rescale_grad=1.0,
+                    clip_gradient=-1.0):
+        """mx.nd.adam_update(weight, grad, mean, var, out=weight, ...): weight, mean and var are updated IN PLACE (mfn_adam_update).
+        lr carries the bias corrections, as MXNet's Adam.update hands it over.  clip_gradient < 0 (or None): no clipping."""
+        (w, g, m, v), n = self._adam_tensors("adam_update", weight, grad, mean, var)
+        self.check(self.ns.adam_update(self.ad.ptr(w), self.ad.ptr(g), self.ad.ptr(m), self.ad.ptr(v), n,
+                                       *self._adam_scalars(lr, beta1, beta2, epsilon, wd, rescale_grad, clip_gradient), self.ad.stream(w)))
+        return weight
+
+    def multi_adam_table(self, weights, grads, means, vars, lr_mults=None, wd_mults=None):
+        """The device-resident table of mfn_multi_adam_update over these tensors (lists of equal length; lr_mults / wd_mults: one
+        float per tensor, default 1): built on the host by mfn_multi_adam_build_table, uploaded once.  It holds addresses: a tensor
+        that moved needs a new table (AdamTable.stale)."""
+        what = "multi_adam_table"
+        T = len(weights)
+        if not T or not (len(grads) == len(means) == len(vars) == T):
+            raise ValueError("%s: one grad, mean and var per weight and at least one tensor, got %d / %d / %d / %d"
+                             % (what, T, len(grads), len(means), len(vars)))
+        for name, mult in (("lr_mults", lr_mults), ("wd_mults", wd_mults)):
+            if mult is not None and len(mult) != T:
+                raise ValueError("%s: %s must have one entry per tensor" % (what, name))
+        rows = [self._adam_tensors(what, *q) for q in zip(weights, grads, means, vars)]
+        ptrs = tuple(tuple(self.ad.ptr(t) for t in ts) for ts, _ in rows)
+        counts = (ctypes.c_longlong * T)(*[n for _, n in rows])
+        cols = [(ctypes.c_void_p * T)(*[p[k] for p in ptrs]) for k in range(4)]
+        lm = None if lr_mults is None else (ctypes.c_float * T)(*[float(x) for x in lr_mults])
+        wm = None if wd_mults is None else (ctypes.c_float * T)(*[float(x) for x in wd_mults])
+        nbytes = self.ns.multi_adam_table_bytes(T, counts)
+        host = (ctypes.c_ulonglong * max(1, (nbytes + 7) // 8))()
+        nb, tag = ctypes.c_int(), ctypes.c_ulonglong()
+        self.check(self.ns.multi_adam_build_table(T, *cols, counts, lm, wm, ctypes.addressof(host), nbytes, ctypes.byref(nb), ctypes.byref(tag)))
+        like = rows[0][0][0]
+        buf = self.ad.empty_bytes(like, max(nbytes, 8))
+        if nbytes:
+            if hasattr(self.ad, "torch"):    # one host-to-device copy on the tensors' device, ordered on the current stream
+                t = self.ad.torch
+                buf[:nbytes // 4].copy_(t.frombuffer(host, dtype=t.float32, count=nbytes // 4))
+            else:                            # host arrays (the emulation): the bytes themselves
+                ctypes.memmove(self.ad.ptr(buf), ctypes.addressof(host), nbytes)
+        return AdamTable(buf, nbytes, tag.value, T, nb.value, ptrs, [n for _, n in rows])
+
+    def multi_adam_update(self, table, lr, beta1=0.9, beta2=0.999, epsilon=1e-8, wd=0.0, rescale_grad=1.0, clip_gradient=-1.0):
+        """adam_update over every tensor of `table` (multi_adam_table) in one launch, in place; a tensor's lr and wd are scaled by
+        its lr_mult and wd_mult."""
+        self.check(self.ns.multi_adam_update(self.ad.ptr(table.buf), table.nbytes, table.tag, table.n_tensors, table.n_blocks,
+                                             *self._adam_scalars(lr, beta1, beta2, epsilon, wd, rescale_grad, clip_gradient),
+                                             self.ad.stream(table.buf)))
+
     def Upsample_backward(self, out_grad, factor, req="write", out=None):
         """Adjoint of Upsample(factor): (N,C,H*f,W*f) -> (N,C,H,W) (mfn_upsample_bwd)."""
         (go,) = self._in(out_grad)
@@ -912,6 +984,18 @@ class PackedDeformWeights:
                              % (self.dims, tuple(dims)))
 
 
+class AdamTable:
+    """Opaque device buffer made by OpSet.multi_adam_table: the tensors' addresses and counts, the launch's blocks, the layout tag."""
+
+    def __init__(self, buf, nbytes, tag, n_tensors, n_blocks, ptrs, counts):
+        self.buf, self.nbytes, self.tag, self.n_tensors, self.n_blocks = buf, int(nbytes), int(tag), int(n_tensors), int(n_blocks)
+        self.ptrs, self.counts = tuple(ptrs), tuple(counts)
+
+    def stale(self, ptrs):
+        """Whether any of these (weight, grad, mean, var) address rows differs from the ones the table was built from."""
+        return tuple(tuple(r) for r in ptrs) != self.ptrs
+
+
 class TorchAdapter:
     """torch-ROCm tensors as device buffers; launches go to torch's current stream."""
 
@@ -1063,6 +1147,18 @@ def multiscale_epe(*a, **k):
 
 def multiscale_epe_backward(*a, **k):
     return default_ops().multiscale_epe_backward(*a, **k)
+
+
+def adam_update(*a, **k):
+    return default_ops().adam_update(*a, **k)
+
+
+def multi_adam_table(*a, **k):
+    return default_ops().multi_adam_table(*a, **k)
+
+
+def multi_adam_update(*a, **k):
+    return default_ops().multi_adam_update(*a, **k)
 
 
 def Convolution(*a, **k):

@@ -283,9 +283,11 @@ class GradientBuckets:
     arrives is all-reduced (sum) at once with async_op=True, so the collective of the decoders' gradients travels over
     RCCL / xGMI while backward is still in the pyramid.  finish() waits for the handles and applies 1 / global_batch.
     Four buckets of ~10.5 MB: large enough for xGMI's per-link bandwidth, few enough launches, early enough first launch.
-    Without a process group (or world 1) only the 1 / global_batch remains."""
+    Without a process group (or world 1) only the 1 / global_batch remains.
+    align: every view starts on a multiple of `align` elements of its bucket (4 = 16 bytes, what Trainer's kernel wants for its
+    16-byte accesses; the padding stays zero and travels with the bucket).  1 packs the views back to back."""
 
-    def __init__(self, params, n_buckets=4, dist=None):
+    def __init__(self, params, n_buckets=4, dist=None, align=1):
         params = [p for p in params if p.requires_grad]
         self.dist = dist if (dist is not None and dist.is_initialized() and dist.get_world_size() > 1) else None
         order = list(reversed(params))
@@ -300,16 +302,21 @@ class GradientBuckets:
                 cur, size = [], 0
         if cur:
             groups.append(cur)
+        align = max(1, int(align))
+        pad = lambda n: (n + align - 1) // align * align
         self.buckets, self.members, self._of, self._hooks = [], groups, {}, []
+        self.offsets = []        # per bucket: the element offset of each member's view
         for bi, grp in enumerate(groups):
-            flat = torch.zeros(sum(p.numel() for p in grp), dtype=grp[0].dtype, device=grp[0].device)
-            off = 0
+            flat = torch.zeros(sum(pad(p.numel()) for p in grp), dtype=grp[0].dtype, device=grp[0].device)
+            off, offs = 0, []
             for p in grp:
                 p.grad = flat[off:off + p.numel()].view_as(p)
-                off += p.numel()
+                offs.append(off)
+                off += pad(p.numel())
                 self._of[p] = bi
                 self._hooks.append(p.register_post_accumulate_grad_hook(self._arrived))
             self.buckets.append(flat)
+            self.offsets.append(offs)
         self._left = [len(g) for g in groups]
         self._handles = []
         self.launch_order = []   # bucket indices in the order their all-reduce was launched by the last backward (tests read it)
@@ -332,8 +339,9 @@ class GradientBuckets:
             if self.dist is not None:
                 self._handles.append(self.dist.all_reduce(self.buckets[bi], op=self.dist.ReduceOp.SUM, async_op=True))
 
-    def finish(self, global_batch):
-        """Behind backward: every bucket reduced (whatever arrived late is launched now), then trainer.step's 1 / batch_size."""
+    def finish(self, global_batch=None, scale=True):
+        """Behind backward: every bucket reduced (whatever arrived late is launched now), then trainer.step's 1 / batch_size.
+        scale=False leaves the sums as they are: Trainer hands 1 / batch_size to its kernel as rescale_grad instead."""
         for bi, left in enumerate(self._left):
             if left > 0:   # parameters that took no gradient this step (frozen branches): their bucket still has to travel
                 self._left[bi] = 0
@@ -343,19 +351,208 @@ class GradientBuckets:
         for h in self._handles:
             h.wait()
         self._handles = []
-        for b in self.buckets:
-            b.mul_(1.0 / float(global_batch))
+        if scale:
+            for b in self.buckets:
+                b.mul_(1.0 / float(global_batch))
 
     def nbytes(self):
         return sum(b.numel() * b.element_size() for b in self.buckets)
+
+
+def reference_named_parameters(net):
+    """[(the reference's parameter name, parameter)] of a module in registration order: the trainable networks keep 'conv1a.weight'
+    as P['conv1a__weight'] and the frozen head of the full model under `head` ('MaskFlownet_S.conv1a.weight'); any other module's
+    names are taken as they are (layer.DeformableConv2D: 'weight', 'bias')."""
+    from .network import HEAD
+    if isinstance(net, MaskFlownetTrainable):
+        return [(HEAD + k, p) for k, p in reference_named_parameters(net.head)] + [(k.replace("__", "."), p) for k, p in net.P.items()]
+    if isinstance(net, MaskFlownetSTrainable):
+        return [(k.replace("__", "."), p) for k, p in net.P.items()]
+    return list(net.named_parameters())
+
+
+def learning_rate_at(schedule, steps):
+    """pipeline.py:65-75: the learning rate of the first entry [boundary, lr] of the schedule (config.optimizer.learning_rate) that
+    `steps` has not passed -- `steps > boundary` moves on, so a boundary step still trains at its own entry's rate --, or None past
+    the last entry (the reference's set_learning_rate returns False there and the run ends)."""
+    i = 0
+    while i < len(schedule) and steps > schedule[i][0]:
+        i += 1
+    return float(schedule[i][1]) if i < len(schedule) else None
+
+
+_ADAM_DEFAULTS = {"learning_rate": 0.001, "beta1": 0.9, "beta2": 0.999, "epsilon": 1e-8, "wd": 0.0, "clip_gradient": None}
+_STATE_KEY = "trainer:adam"      # the float64 array of save_states: num_update, then the hyper-parameters in this order
+_STATE_FIELDS = ("num_update", "learning_rate", "beta1", "beta2", "epsilon", "wd", "clip_gradient")
+
+
+class Trainer:
+    """gluon.Trainer(params, 'adam', {'learning_rate': 1e-4}) of pipeline.py:27 with MXNet's arithmetic, the whole step one launch of
+    mfn_multi_adam_update (kernels/optimizer.h).  named_params: {name: parameter} or (name, parameter) pairs, the names the
+    reference's (reference_named_parameters); only parameters with requires_grad are taken -- `fix_head` (main.py:139): a frozen
+    head and its would-be state are never touched.  optimizer_params: learning_rate, beta1 (0.9), beta2 (0.999), epsilon (1e-8),
+    wd (0), clip_gradient (None), MXNet's names and defaults; lr_mult / wd_mult: {name: factor}, default 1.
+    The trainer owns a GradientBuckets(align=4) over its parameters (`.buckets`: p.grad is a view, zero them with buckets.zero())
+    and flat zero-initialised mean and var buffers in the same layout.  step(batch_size): the exchange is finished unscaled, num_update
+    advances (one count for all parameters: every one is updated at every step, so MXNet's per-index counts are equal), lr_t =
+    lr * sqrt(1 - beta2^t) / (1 - beta1^t) is formed in Python doubles as Adam.update does, and the kernel gets rescale_grad =
+    1 / batch_size; then every updated parameter's version counter advances (the kernel writes through raw pointers, and caches such
+    as layer.DeformableConv2D._packed key on it)."""
+
+    def __init__(self, named_params, optimizer="adam", optimizer_params=None, n_buckets=4, dist=None):
+        if optimizer != "adam":
+            raise ValueError("Trainer: only 'adam' (pipeline.py:27) is implemented, got %r" % (optimizer,))
+        hp = dict(_ADAM_DEFAULTS)
+        hp.update(optimizer_params or {})
+        unknown = sorted(set(hp) - set(_ADAM_DEFAULTS) - {"lr_mult", "wd_mult"})
+        if unknown:
+            raise ValueError("Trainer: unknown optimizer parameters %s" % unknown)
+        self._lr_mult, self._wd_mult = dict(hp.pop("lr_mult", None) or {}), dict(hp.pop("wd_mult", None) or {})
+        self._hp = hp
+        pairs = list(named_params.items()) if hasattr(named_params, "items") else list(named_params)
+        pairs = [(k, p) for k, p in pairs if p.requires_grad]
+        if not pairs:
+            raise ValueError("Trainer: no parameter with requires_grad")
+        self.names, self.params = [k for k, _ in pairs], [p for _, p in pairs]
+        if len(set(self.names)) != len(self.names):
+            raise ValueError("Trainer: parameter names must be unique")
+        for k, p in pairs:
+            if not p.is_contiguous() or p.dtype != torch.float32:
+                raise ValueError("Trainer: parameter %s must be a contiguous float32 tensor" % k)
+        self.buckets = GradientBuckets(self.params, n_buckets=n_buckets, dist=dist, align=4)
+        self._mean = [torch.zeros_like(b) for b in self.buckets.buckets]
+        self._var = [torch.zeros_like(b) for b in self.buckets.buckets]
+        where = {}
+        for bi, (grp, offs) in enumerate(zip(self.buckets.members, self.buckets.offsets)):
+            for p, off in zip(grp, offs):
+                where[p] = (bi, off)
+        view = lambda flats, p: flats[where[p][0]][where[p][1]:where[p][1] + p.numel()].view_as(p)
+        self.mean = {k: view(self._mean, p) for k, p in pairs}      # views into the flat buffers, by name
+        self.var = {k: view(self._var, p) for k, p in pairs}
+        self.num_update = 0
+        self._table = None
+
+    # ---- gluon.Trainer's surface ---------------------------------------------------------------------------------------------
+    @property
+    def learning_rate(self):
+        return self._hp["learning_rate"]
+
+    def set_learning_rate(self, lr):
+        self._hp["learning_rate"] = float(lr)
+
+    def lr_t(self, t=None):
+        """What Adam.update hands to the operator at update count t (default: the next step's), rounded once to fp32."""
+        t = self.num_update + 1 if t is None else int(t)
+        coef1 = 1.0 - self._hp["beta1"] ** t
+        coef2 = 1.0 - self._hp["beta2"] ** t
+        return float(np.float32(self._hp["learning_rate"] * np.sqrt(coef2) / coef1))
+
+    def _rows(self):
+        return [(p, p.grad, self.mean[k], self.var[k]) for k, p in zip(self.names, self.params)]
+
+    def step(self, batch_size):
+        """trainer.step(batch_size), pipeline.py:114."""
+        rows = self._rows()
+        for k, (p, g, _, _) in zip(self.names, rows):
+            if g is None or g.shape != p.shape or not g.is_contiguous():
+                raise RuntimeError("Trainer.step: the gradient of %s no longer views its bucket (zero the gradients with trainer.buckets.zero())" % k)
+        self.buckets.finish(scale=False)
+        ptrs = [tuple(t.data_ptr() for t in r) for r in rows]
+        if self._table is None or self._table.stale(ptrs):      # rebuilt and uploaded only when an address in it changed
+            self._table = ops.multi_adam_table(*zip(*rows), lr_mults=[self._lr_mult.get(k, 1.0) for k in self.names],
+                                               wd_mults=[self._wd_mult.get(k, 1.0) for k in self.names])
+        self.num_update += 1
+        hp = self._hp
+        ops.multi_adam_update(self._table, self.lr_t(self.num_update), hp["beta1"], hp["beta2"], hp["epsilon"], hp["wd"],
+                              1.0 / float(batch_size), hp["clip_gradient"])
+        for p in self.params:
+            torch.autograd.graph.increment_version(p)
+
+    def save_states(self, path):
+        """trainer.save_states (pipeline.py:54).  MXNet's .states is a pickle of MXNet objects; this file is the project's own: the
+        NDArray-list container of io.save_params with 'mean:<name>' and 'var:<name>' per parameter and one float64 array
+        'trainer:adam' = (num_update, learning_rate, beta1, beta2, epsilon, wd, clip_gradient or -1)."""
+        from . import io
+        out = {}
+        for k in self.names:
+            out["mean:" + k] = self.mean[k].detach().cpu().numpy()
+            out["var:" + k] = self.var[k].detach().cpu().numpy()
+        hp = self._hp
+        clip = -1.0 if hp["clip_gradient"] is None else float(hp["clip_gradient"])
+        out[_STATE_KEY] = np.array([self.num_update, hp["learning_rate"], hp["beta1"], hp["beta2"], hp["epsilon"], hp["wd"], clip], np.float64)
+        io.save_params(path, out)
+
+    def load_states(self, path):
+        """trainer.load_states (main.py:143): refuses missing names, unexpected names and wrong shapes before it changes anything."""
+        from . import io
+        got = io.load_params(path)
+        want = [pre + k for k in self.names for pre in ("mean:", "var:")] + [_STATE_KEY]
+        missing = [k for k in want if k not in got]
+        unexpected = [k for k in got if k not in set(want)]
+        if missing:
+            raise KeyError("load_states: %s lacks %s" % (path, missing))
+        if unexpected:
+            raise KeyError("load_states: %s has entries without a parameter here: %s" % (path, unexpected))
+        for k, p in zip(self.names, self.params):
+            for pre in ("mean:", "var:"):
+                if tuple(got[pre + k].shape) != tuple(p.shape) or got[pre + k].dtype != np.float32:
+                    raise ValueError("load_states: %s%s is %s %s, the parameter %s float32" % (pre, k, got[pre + k].dtype, got[pre + k].shape, tuple(p.shape)))
+        st = got[_STATE_KEY]
+        if st.shape != (len(_STATE_FIELDS),) or st.dtype != np.float64:
+            raise ValueError("load_states: %s must be %d float64 values" % (_STATE_KEY, len(_STATE_FIELDS)))
+        for k in self.names:
+            self.mean[k].copy_(torch.from_numpy(got["mean:" + k]))
+            self.var[k].copy_(torch.from_numpy(got["var:" + k]))
+        self.num_update = int(st[0])
+        for name, v in zip(_STATE_FIELDS[1:], st[1:]):
+            self._hp[name] = float(v)
+        if self._hp["clip_gradient"] < 0:
+            self._hp["clip_gradient"] = None
+
+
+def save_checkpoint(prefix, net, trainer):
+    """pipeline.py:52-54: network.save_parameters(prefix + '.params') under the reference's names, trainer.save_states(prefix + '.states')."""
+    from . import io
+    io.save_params(prefix + ".params", {k: p.detach().cpu().numpy() for k, p in reference_named_parameters(net)})
+    trainer.save_states(prefix + ".states")
+
+
+def load_checkpoint(prefix, net, trainer=None):
+    """pipeline.py:56-57 and main.py:143: the parameters of prefix + '.params' into `net` (in place: their addresses, and with them
+    the trainer's table, stay), then the trainer's states of prefix + '.states'."""
+    from . import io
+    got = io.load_params(prefix + ".params")
+    own = reference_named_parameters(net)
+    missing = [k for k, _ in own if k not in got]
+    unexpected = [k for k in got if k not in {k for k, _ in own}]
+    if missing or unexpected:
+        raise KeyError("load_checkpoint: %s.params lacks %s and has %s without a parameter" % (prefix, missing, unexpected))
+    with torch.no_grad():
+        for k, p in own:
+            if tuple(got[k].shape) != tuple(p.shape):
+                raise ValueError("load_checkpoint: %s has shape %s, the parameter %s" % (k, got[k].shape, tuple(p.shape)))
+            p.copy_(torch.from_numpy(np.ascontiguousarray(got[k])))
+    if trainer is not None:
+        trainer.load_states(prefix + ".states")
 
 
 def train_step(net, loss_fn, opt, im1, im2, label, mask, buckets=None, global_batch=None):
     """pipeline.py:95-114: forward, loss, `loss.backward()` (the per-sample losses summed), the gradient exchange, and
     `trainer.step(batch_size)` -- the optimizer sees (sum over the GLOBAL batch of the per-sample gradients) / global_batch.
     buckets: a GradientBuckets over net.parameters() (its all-reduces start inside backward); None = one device, the gradients
-    scaled in place.  global_batch defaults to this call's batch (one device).  Returns the per-sample loss of the local shard."""
+    scaled in place.  global_batch defaults to this call's batch (one device).  Returns the per-sample loss of the local shard.
+    opt: a torch optimizer, or a Trainer -- then its own buckets carry the gradients (`buckets` must be None or those) and the step is
+    opt.step(global_batch): MXNet's Adam in one launch, the 1 / global_batch inside it."""
     gb = int(global_batch if global_batch is not None else im1.shape[0])
+    if isinstance(opt, Trainer):
+        if buckets is not None and buckets is not opt.buckets:
+            raise ValueError("train_step: a Trainer brings its own gradient buckets")
+        opt.buckets.zero()
+        preds, _ = net(im1, im2)
+        loss = loss_fn(label, mask, *preds)
+        loss.sum().backward()
+        opt.step(gb)
+        return loss.detach()
     if buckets is not None:
         buckets.zero()
     else:

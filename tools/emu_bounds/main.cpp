@@ -3,6 +3,7 @@
 // Python, nothing is preloaded, no GPU is involved.  tests/test_memory_contract.py sees writes next to a buffer and reads that reach a
 // result; here the sanitizer sees every access outside a block at any distance, discarded over-reads and the emulated LDS included.
 // The list is one call per kernel family and route of that test, driven by the tables below; built and run by tools/emu_bounds.py.
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -48,6 +49,10 @@
 #define mfn_multiscale_epe_workspace_bytes mfn_emu_multiscale_epe_workspace_bytes
 #define mfn_multiscale_epe_fwd mfn_emu_multiscale_epe_fwd
 #define mfn_multiscale_epe_bwd mfn_emu_multiscale_epe_bwd
+#define mfn_adam_update mfn_emu_adam_update
+#define mfn_multi_adam_table_bytes mfn_emu_multi_adam_table_bytes
+#define mfn_multi_adam_build_table mfn_emu_multi_adam_build_table
+#define mfn_multi_adam_update mfn_emu_multi_adam_update
 #define mfn_conv2d_out_shape mfn_emu_conv2d_out_shape
 #define mfn_conv2d_workspace_bytes mfn_emu_conv2d_workspace_bytes
 #define mfn_conv2d_packed_weight_bytes mfn_emu_conv2d_packed_weight_bytes
@@ -298,6 +303,35 @@ static void others() {
     snprintf(name, sizeof(name), "%s bwd", r.name);
     report(name, mfn_multiscale_epe_bwd(gloss.f(), preds, fs, wts, 2, lab.f(), mask.f(), r.scalar_mask, 1e-8f, r.robust, 0.4f, sums.f(), gp, reqs, r.N, H,
                                         W, nullptr));
+  }
+  // the trainer's Adam step: every count around a block of 4096 elements, each tensor a heap block of its exact size (the 16-byte
+  // route with its scalar tail), then the same tensors one float into blocks one float longer (the one-element route), single and multi
+  {
+    const long long counts[8] = {2 * 4096 + 7, 1, 4097, 3, 4, 5, 4095, 4096};
+    for (int shift = 0; shift < 2; ++shift) {
+      std::vector<Tensor *> own;
+      float *w[8], *m[8], *v[8];
+      const float *g[8];
+      for (int i = 0; i < 8; ++i) {
+        Tensor *t[4];
+        for (int k = 0; k < 4; ++k) own.push_back(t[k] = new Tensor((size_t)counts[i] + shift));
+        for (size_t e = 0; e < t[3]->n; ++e) t[3]->f()[e] = fabsf(t[3]->f()[e]);
+        w[i] = t[0]->f() + shift; g[i] = t[1]->f() + shift; m[i] = t[2]->f() + shift; v[i] = t[3]->f() + shift;
+      }
+      char name[96];
+      for (int i = 0; i < 8; ++i) {
+        snprintf(name, sizeof(name), "adam_update n = %lld%s", counts[i], shift ? ", unaligned" : "");
+        report(name, mfn_adam_update(w[i], g[i], m[i], v[i], counts[i], 1e-4f, 0.9f, 0.999f, 1e-8f, 1e-2f, 0.5f, 1.f, nullptr));
+      }
+      const size_t need = mfn_multi_adam_table_bytes(8, counts);
+      Block table(need);
+      int nb = 0;
+      unsigned long long tag = 0;
+      int rc = mfn_multi_adam_build_table(8, w, g, m, v, counts, nullptr, nullptr, table.p, need, &nb, &tag);
+      snprintf(name, sizeof(name), "multi_adam_update, 8 tensors%s", shift ? ", unaligned" : "");
+      report(name, rc ? rc : mfn_multi_adam_update(table.p, need, tag, 8, nb, 1e-4f, 0.9f, 0.999f, 1e-8f, 1e-2f, 0.5f, 1.f, nullptr));
+      for (Tensor *t : own) delete t;
+    }
   }
 }
 
