@@ -394,6 +394,34 @@ int mfn_multi_adam_update(const void *table_dev, size_t table_bytes, unsigned lo
                           float beta1, float beta2, float epsilon, float wd, float rescale_grad, float clip_gradient, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * One training batch cut out of a device-resident data set -- replaces what iterate_data and batch_samples
+ * of the reference's main.py:466-486 do to the N samples of a batch on the host (crop, HWC -> CHW, the reversed W axis with the
+ * negated first label channel, np.stack) and the upload of the result.  One launch, the same bytes:
+ *   out[n, c, y, x] = src_n[y0_n + y, x0_n + (flip_n ? Wc - 1 - x : x), c]
+ * Sources per slot n, HWC and contiguous: img1, img2 uint8 (Hs,Ws,3); flow (Hs,Ws,2), fp32 (label_type 0) or fp16 (1, widened
+ * exactly); mask uint8 (Hs,Ws,1) or NULL.  Sizes, crop origin, flip and label type are per slot.  Outputs, contiguous NCHW:
+ * img1, img2 (N,3,Hc,Wc) uint8; label (N,2,Hc,Wc) fp32 in the readers' (u, v) order, channel 0 with its sign bit flipped where
+ * flip is set (+0.0 -> -0.0); mask (N,1,Hc,Wc) uint8 when with_mask != 0 -- a slot whose mask is NULL writes 255 -- and not
+ * touched (may be NULL) otherwise.
+ * READ CONTRACT: every source array starts at a 16-byte aligned address and is readable up to the next multiple of 16 bytes of
+ * its size; the kernel reads aligned words inside that extent and nothing outside it.
+ * mfn_batch_gather_build_rows checks the slots and fills a caller-owned HOST table (8-byte aligned, mfn_batch_gather_rows_bytes(N)
+ * bytes: 64 per slot) from HOST arrays of DEVICE addresses (`mask` may be NULL: no slot has one); the caller uploads the bytes as
+ * they are, once per step: the library allocates nothing and synchronises nothing.  The tag binds the table to (N, Hc, Wc).
+ * Errors before any launch: a NULL required pointer or array, a NULL img1 / img2 / flow of a slot (MFN_E_NULL); N, Hc, Wc, Hs or
+ * Ws <= 0, a crop that leaves its source (y0 < 0, y0 + Hc > Hs, x0 < 0, x0 + Wc > Ws), a table byte count or tag that does not
+ * fit (MFN_E_SHAPE); a source address that is not 16-byte aligned, an output tensor that is not 4-byte aligned, a table that is
+ * not 8-byte aligned (MFN_E_ALIGN); a label type other than 0 / 1, a flip other than 0 / 1 (MFN_E_PARAM); N > 65535 or
+ * Hc * Wc >= 2^31 (MFN_E_UNSUPPORTED).  mfn_batch_gather_rows_bytes returns 0 for N <= 0. */
+size_t mfn_batch_gather_rows_bytes(int N);
+int mfn_batch_gather_build_rows(int N, const void *const *img1, const void *const *img2, const void *const *flow,
+                                const void *const *mask, const int *Hs, const int *Ws, const int *label_type, const int *y0,
+                                const int *x0, const int *flip, int Hc, int Wc, void *rows_host, size_t rows_bytes,
+                                unsigned long long *tag);
+int mfn_batch_gather(const void *rows_dev, size_t rows_bytes, unsigned long long tag, int N, int Hc, int Wc, int with_mask,
+                     unsigned char *img1, unsigned char *img2, float *label, unsigned char *mask, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Convolution / Deconvolution -- replace the Gluon blocks of
  * /root/reference/network/MaskFlownet.py:79-163: nn.Conv2D(channels, kernel_size=3, strides, padding, dilation)
  * [+ LeakyReLU(0.1)] of conv() / predict_flow() / predict_mask() (:165-191) and nn.Conv2DTranspose(channels, 4, 2, 1)

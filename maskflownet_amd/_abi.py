@@ -73,6 +73,10 @@ SIGNATURES = {
     "multi_adam_build_table": (_i, [_i] + [C.POINTER(C.c_void_p)] * 4 + [C.POINTER(C.c_longlong), C.POINTER(C.c_float), C.POINTER(C.c_float),
                                         C.c_void_p, C.c_size_t, _pi, C.POINTER(C.c_ulonglong)]),
     "multi_adam_update": (_i, [C.c_void_p, C.c_size_t, C.c_ulonglong, _i, _i] + [C.c_float] * 7 + [_s]),
+    # one training batch out of a device-resident data set (kernels/batch.h); the rows entries are host-only
+    "batch_gather_rows_bytes": (C.c_size_t, [_i]),
+    "batch_gather_build_rows": (_i, [_i] + [C.POINTER(C.c_void_p)] * 4 + [_pi] * 6 + [_i, _i, C.c_void_p, C.c_size_t, C.POINTER(C.c_ulonglong)]),
+    "batch_gather": (_i, [C.c_void_p, C.c_size_t, C.c_ulonglong] + [_i] * 4 + [C.c_void_p] * 4 + [_s]),
     "set_arithmetic": (_i, [C.c_char_p, _i]),
     "get_arithmetic": (_i, [C.c_char_p, _pi]),
     "set_tuning": (_i, [C.c_char_p, _i]),

@@ -22,6 +22,7 @@
 #include "kernels/augment.h"
 #include "kernels/loss.h"
 #include "kernels/optimizer.h"
+#include "kernels/batch.h"
 #include "kernels/backward.h"
 #include "kernels/dc_backward.h"
 #include "kernels/conv.h"
@@ -1944,6 +1945,64 @@ int MFN_API(multi_adam_update)(const void *table_dev, size_t table_bytes, unsign
   return hipfail(multi_adam_update_launch(table_dev, (unsigned)n_tensors, (unsigned)n_blocks,
                                           AdamHyper{lr, beta1, beta2, epsilon, wd, rescale_grad, clip_gradient}, (hipStream_t)stream),
                  "multi_adam_update");
+}
+
+// ---- one training batch out of a device-resident data set (kernels/batch.h) ---------------------------------------------------
+size_t MFN_API(batch_gather_rows_bytes)(int N) { return batch_rows_bytes(N); }
+
+int MFN_API(batch_gather_build_rows)(int N, const void *const *img1, const void *const *img2, const void *const *flow,
+                                     const void *const *mask, const int *Hs, const int *Ws, const int *label_type, const int *y0,
+                                     const int *x0, const int *flip, int Hc, int Wc, void *rows_host, size_t rows_bytes,
+                                     unsigned long long *tag) {
+  const char *what = "batch_gather_build_rows";
+  if (N <= 0 || Hc <= 0 || Wc <= 0) return fail(MFN_E_SHAPE, "%s: N=%d Hc=%d Wc=%d", what, N, Hc, Wc);
+  if (N > 65535 || (long long)Hc * Wc > 0x7FFFFFFFll) return fail(MFN_E_UNSUPPORTED, "%s: N=%d, crop %dx%d is more than one launch covers", what, N, Hc, Wc);
+  if (!img1 || !img2 || !flow || !Hs || !Ws || !label_type || !y0 || !x0 || !flip) return fail(MFN_E_NULL, "%s: NULL host array", what);
+  if (!rows_host || !tag) return fail(MFN_E_NULL, "%s: NULL output (rows_host, tag)", what);
+  if (rows_bytes < batch_rows_bytes(N)) return fail(MFN_E_SHAPE, "%s: a table of %zu bytes needed, %zu given", what, batch_rows_bytes(N), rows_bytes);
+  if (!aligned(rows_host, 8)) return fail(MFN_E_ALIGN, "%s: the table must be 8-byte aligned", what);
+  for (int n = 0; n < N; ++n) {
+    const void *m = mask ? mask[n] : nullptr;
+    if (!img1[n] || !img2[n] || !flow[n]) return fail(MFN_E_NULL, "%s: slot %d has a NULL img1, img2 or flow", what, n);
+    if (!aligned(img1[n], 16) || !aligned(img2[n], 16) || !aligned(flow[n], 16) || !aligned(m, 16))
+      return fail(MFN_E_ALIGN, "%s: the source arrays of slot %d must be 16-byte aligned", what, n);
+    if (label_type[n] != BATCH_LABEL_F32 && label_type[n] != BATCH_LABEL_F16)
+      return fail(MFN_E_PARAM, "%s: label type %d of slot %d (0 = fp32, 1 = fp16)", what, label_type[n], n);
+    if (flip[n] != 0 && flip[n] != 1) return fail(MFN_E_PARAM, "%s: flip %d of slot %d (0 or 1)", what, flip[n], n);
+    if (Hs[n] <= 0 || Ws[n] <= 0) return fail(MFN_E_SHAPE, "%s: slot %d is %dx%d", what, n, Hs[n], Ws[n]);
+    if (y0[n] < 0 || x0[n] < 0 || (long long)y0[n] + Hc > Hs[n] || (long long)x0[n] + Wc > Ws[n])
+      return fail(MFN_E_SHAPE, "%s: the crop %dx%d at (%d, %d) leaves the %dx%d source of slot %d", what, Hc, Wc, y0[n], x0[n], Hs[n], Ws[n], n);
+  }
+  for (int n = 0; n < N; ++n) {
+    BatchRow r{};
+    r.img1 = (const unsigned char *)img1[n]; r.img2 = (const unsigned char *)img2[n]; r.flow = flow[n];
+    r.mask = (const unsigned char *)(mask ? mask[n] : nullptr);
+    r.Hs = Hs[n]; r.Ws = Ws[n]; r.y0 = y0[n]; r.x0 = x0[n];
+    r.flip = (unsigned)flip[n]; r.label_type = (unsigned)label_type[n];
+    memcpy((char *)rows_host + (size_t)n * sizeof(BatchRow), &r, sizeof(r));
+  }
+  *tag = batch_rows_tag(N, Hc, Wc);
+  return 0;
+}
+
+int MFN_API(batch_gather)(const void *rows_dev, size_t rows_bytes, unsigned long long tag, int N, int Hc, int Wc, int with_mask,
+                          unsigned char *img1, unsigned char *img2, float *label, unsigned char *mask, void *stream) {
+  if (N <= 0 || Hc <= 0 || Wc <= 0) return fail(MFN_E_SHAPE, "batch_gather: N=%d Hc=%d Wc=%d", N, Hc, Wc);
+  if (!rows_dev || !img1 || !img2 || !label) return fail(MFN_E_NULL, "batch_gather: NULL table or output");
+  if (with_mask && !mask) return fail(MFN_E_NULL, "batch_gather: NULL mask output in a call with a mask");
+  if (N > 65535 || (long long)Hc * Wc > 0x7FFFFFFFll) return fail(MFN_E_UNSUPPORTED, "batch_gather: N=%d, crop %dx%d is more than one launch covers", N, Hc, Wc);
+  if (rows_bytes != batch_rows_bytes(N)) return fail(MFN_E_SHAPE, "batch_gather: a table of %zu bytes expected for N=%d, %zu given", batch_rows_bytes(N), N, rows_bytes);
+  if (tag != batch_rows_tag(N, Hc, Wc))
+    return fail(MFN_E_SHAPE, "batch_gather: the table (tag %llx) was not built for N=%d and a %dx%d crop: re-run mfn_batch_gather_build_rows", tag, N, Hc, Wc);
+  if (!aligned(rows_dev, 8)) return fail(MFN_E_ALIGN, "batch_gather: the table must be 8-byte aligned");
+  if (!aligned(img1, 4) || !aligned(img2, 4) || !aligned(label, 4) || (with_mask && !aligned(mask, 4)))
+    return fail(MFN_E_ALIGN, "batch_gather: the output tensors must be 4-byte aligned");
+  BatchGatherParams p{};
+  p.rows = (const BatchRow *)rows_dev;
+  p.img1 = img1; p.img2 = img2; p.label = (unsigned *)label; p.mask = with_mask ? mask : nullptr;
+  p.N = N; p.Hc = Hc; p.Wc = Wc;
+  p.label16 = aligned(label, 16) ? 1u : 0u;
+  return hipfail(batch_gather_launch(p, (hipStream_t)stream), "batch_gather");
 }
 
 int MFN_API(leaky_relu_bwd)(const float *gout, const float *y, float *gin, size_t n, float slope, void *stream) {

@@ -4,6 +4,9 @@
   endian (/root/reference/reader/chairs/flo.py:4-25 hard-codes the 512x384 header; reader/sintel.py:46-73 reads the
   general one).  `.flo` stores (u, v) = (dx, dy); the network uses channel 0 = dy (pipeline.py:105,176,219), so
   `flo_to_network` / `network_to_flo` do the flip and the HWC <-> CHW move.
+* Binary PPM (`P6`), the FlyingChairs images: `P6`, width, height, maxval as decimal text separated by white space
+  (`#` comments allowed), ONE white-space byte, then H*W RGB triples.  reader/chairs/ppm.py accepts only the literal
+  header `P6 512 384 255\n`; `read_ppm` reads any size at maxval 255.
 * MXNet `.params` (`save_parameters`, pipeline.py:52-63): an NDArray list -- uint64 magic 0x112, uint64 reserved,
   uint64 count, count x NDArray, uint64 name count, names as uint64 length + bytes.  An NDArray (V2, magic 0xF993FAC9)
   is int32 storage type (0 = dense), shape as uint32 ndim + int64 dims, context (int32 dev_type, int32 dev_id), int32
@@ -39,6 +42,41 @@ def read_flo(path):
     if data.size != 2 * w * h:
         raise ValueError("%s: truncated .flo payload" % path)
     return data.reshape(h, w, 2).astype(np.float32, copy=False)
+
+
+def read_ppm(path):
+    """Binary PPM (P6, maxval 255) of any size -> (H, W, 3) uint8, as reader/chairs/ppm.py returns it for 512x384."""
+    with open(path, "rb") as f:
+        buf = f.read()
+    pos, fields = 0, []
+    while len(fields) < 4:
+        while pos < len(buf) and buf[pos:pos + 1].isspace():
+            pos += 1
+        if buf[pos:pos + 1] == b"#":                 # a comment runs to the end of its line
+            while pos < len(buf) and buf[pos:pos + 1] != b"\n":
+                pos += 1
+            continue
+        end = pos
+        while end < len(buf) and not buf[end:end + 1].isspace():
+            end += 1
+        if end == pos:
+            raise ValueError("%s: truncated PPM header" % path)
+        fields.append(buf[pos:end])
+        pos = end
+    if fields[0] != b"P6":
+        raise ValueError("%s: bad PPM magic %r (expected b'P6')" % (path, fields[0][:8]))
+    try:
+        w, h, maxval = (int(v) for v in fields[1:])
+    except ValueError:
+        raise ValueError("%s: bad PPM header fields %r" % (path, fields[1:])) from None
+    if maxval != 255:
+        raise ValueError("%s: PPM maxval %d (only 255 is read)" % (path, maxval))
+    if w <= 0 or h <= 0 or w > 99999 or h > 99999:
+        raise ValueError("%s: implausible PPM size %dx%d" % (path, w, h))
+    pos += 1                                          # the single white-space byte behind maxval
+    if len(buf) - pos < 3 * w * h:
+        raise ValueError("%s: truncated PPM payload (%d of %d bytes)" % (path, max(0, len(buf) - pos), 3 * w * h))
+    return np.frombuffer(buf, np.uint8, 3 * w * h, pos).reshape(h, w, 3).copy()
 
 
 def write_flo(path, flow_hw2):

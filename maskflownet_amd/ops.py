@@ -55,6 +55,17 @@ class OpSet:
         del self._retired[:]
         return n
 
+    def _upload(self, like, host, nbytes):
+        """`nbytes` (a multiple of 4) of a ctypes host buffer in a fresh device buffer next to `like`: a table built on the host."""
+        buf = self.ad.empty_bytes(like, max(nbytes, 8))
+        if nbytes:
+            if hasattr(self.ad, "torch"):    # one host-to-device copy on the tensors' device, ordered on the current stream
+                t = self.ad.torch
+                buf[:nbytes // 4].copy_(t.frombuffer(host, dtype=t.float32, count=nbytes // 4))
+            else:                            # host arrays (the emulation): the bytes themselves
+                ctypes.memmove(self.ad.ptr(buf), ctypes.addressof(host), nbytes)
+        return buf
+
     def _out(self, out, like, shape, what):
         """A caller-supplied destination goes to the kernel as it is: it must already be what the kernel writes --
         float32, contiguous NCHW of exactly `shape`, on the inputs' device (no silent copy, no reshaping)."""
@@ -710,15 +721,7 @@ class OpSet:
         host = (ctypes.c_ulonglong * max(1, (nbytes + 7) // 8))()
         nb, tag = ctypes.c_int(), ctypes.c_ulonglong()
         self.check(self.ns.multi_adam_build_table(T, *cols, counts, lm, wm, ctypes.addressof(host), nbytes, ctypes.byref(nb), ctypes.byref(tag)))
-        like = rows[0][0][0]
-        buf = self.ad.empty_bytes(like, max(nbytes, 8))
-        if nbytes:
-            if hasattr(self.ad, "torch"):    # one host-to-device copy on the tensors' device, ordered on the current stream
-                t = self.ad.torch
-                buf[:nbytes // 4].copy_(t.frombuffer(host, dtype=t.float32, count=nbytes // 4))
-            else:                            # host arrays (the emulation): the bytes themselves
-                ctypes.memmove(self.ad.ptr(buf), ctypes.addressof(host), nbytes)
-        return AdamTable(buf, nbytes, tag.value, T, nb.value, ptrs, [n for _, n in rows])
+        return AdamTable(self._upload(rows[0][0][0], host, nbytes), nbytes, tag.value, T, nb.value, ptrs, [n for _, n in rows])
 
     def multi_adam_update(self, table, lr, beta1=0.9, beta2=0.999, epsilon=1e-8, wd=0.0, rescale_grad=1.0, clip_gradient=-1.0):
         """adam_update over every tensor of `table` (multi_adam_table) in one launch, in place; a tensor's lr and wd are scaled by
@@ -726,6 +729,100 @@ class OpSet:
         self.check(self.ns.multi_adam_update(self.ad.ptr(table.buf), table.nbytes, table.tag, table.n_tensors, table.n_blocks,
                                              *self._adam_scalars(lr, beta1, beta2, epsilon, wd, rescale_grad, clip_gradient),
                                              self.ad.stream(table.buf)))
+
+    # ---- one training batch out of a device-resident data set (main.py:466-486) -----------------------------------------------------
+    _BATCH_LABEL = {"float32": 0, "float16": 1}
+
+    def _raw(self, a, what, dtypes, shape=None):
+        """A uint8 / float16 / float32 device array as it is (the adapters' prepare insists on float32): -> its dtype's name.  Dense
+        and C-ordered; `shape`, where given, is what it must have."""
+        if hasattr(self.ad, "torch") and not isinstance(a, self.ad.torch.Tensor):
+            raise TypeError("%s: expected a torch.Tensor on a ROCm device, got %r" % (what, type(a)))
+        if getattr(a, "is_cuda", True) is False:
+            raise RuntimeError("maskflownet_amd ops run on the MI355X only: %s is on %s (there is no CPU fallback)" % (what, a.device))
+        name = str(getattr(a, "dtype", type(a))).split(".")[-1]
+        if name not in dtypes:
+            raise TypeError("%s: %s expected, got %s" % (what, " or ".join(dtypes), name))
+        got = self.ad.shape(a)
+        if shape is not None and got != tuple(shape):
+            raise ValueError("%s: shape %s, expected %s" % (what, got, tuple(shape)))
+        st = 1
+        for d, have in zip(reversed(got), reversed(self.ad.elem_strides(a))):
+            if d > 1 and have != st:
+                raise ValueError("%s must be contiguous (strides %s)" % (what, self.ad.elem_strides(a)))
+            st *= int(d)
+        return name
+
+    def batch_gather_rows(self, samples, crop_shape, origins, flips):
+        """The device-resident table of mfn_batch_gather for one batch: one slot per entry of `samples`, each (img1, img2, flow, mask
+        or None) of device arrays in the readers' HWC layout -- img1, img2 uint8 (Hs,Ws,3), flow float32 or float16 (Hs,Ws,2), mask uint8
+        (Hs,Ws) or (Hs,Ws,1); origins: (y0, x0) per slot; flips: 0 / 1 per slot.  Built and checked on the host by
+        mfn_batch_gather_build_rows (a crop that leaves its source, a source that is not 16-byte aligned: refused), uploaded once.
+        Every source must be readable up to the next multiple of 16 bytes of its size (data.DeviceDataset pads it so)."""
+        what = "batch_gather_rows"
+        N = len(samples)
+        Hc, Wc = (int(v) for v in crop_shape)
+        if not N or len(origins) != N or len(flips) != N:
+            raise ValueError("%s: one origin and one flip per sample and at least one sample, got %d / %d / %d" % (what, N, len(origins), len(flips)))
+        ptrs, Hs, Ws, lt = [[], [], [], []], [], [], []
+        for n, smp in enumerate(samples):
+            img1, img2, flow, mask = smp
+            self._raw(img1, "%s: img1 of slot %d" % (what, n), ("uint8",))
+            shp = self.ad.shape(img1)
+            if len(shp) != 3 or shp[2] != 3:
+                raise ValueError("%s: img1 of slot %d has shape %s, expected (Hs, Ws, 3)" % (what, n, shp))
+            h, w = int(shp[0]), int(shp[1])
+            self._raw(img2, "%s: img2 of slot %d" % (what, n), ("uint8",), (h, w, 3))
+            lt.append(self._BATCH_LABEL[self._raw(flow, "%s: flow of slot %d" % (what, n), ("float32", "float16"), (h, w, 2))])
+            if mask is not None:
+                self._raw(mask, "%s: mask of slot %d" % (what, n), ("uint8",), (h, w, 1) if len(self.ad.shape(mask)) == 3 else (h, w))
+            for col, a in zip(ptrs, (img1, img2, flow, mask)):
+                col.append(None if a is None else self.ad.ptr(a))
+            Hs.append(h)
+            Ws.append(w)
+        ints = lambda v: (ctypes.c_int * N)(*[int(x) for x in v])
+        cols = [(ctypes.c_void_p * N)(*c) for c in ptrs]
+        nbytes = self.ns.batch_gather_rows_bytes(N)
+        host = (ctypes.c_ulonglong * (nbytes // 8))()
+        tag = ctypes.c_ulonglong()
+        self.check(self.ns.batch_gather_build_rows(N, *cols, ints(Hs), ints(Ws), ints(lt), ints([o[0] for o in origins]),
+                                                   ints([o[1] for o in origins]), ints(flips), Hc, Wc, ctypes.addressof(host), nbytes,
+                                                   ctypes.byref(tag)))
+        return BatchRows(self._upload(samples[0][0], host, nbytes), nbytes, tag.value, N, (Hc, Wc), samples)
+
+    def batch_gather(self, rows, crop_shape, with_mask, out=None):
+        """One batch in one launch (mfn_batch_gather): -> (img1, img2 (N,3,Hc,Wc) uint8, label (N,2,Hc,Wc) float32 in the readers' (u, v)
+        order, mask (N,1,Hc,Wc) uint8 or None), exactly what main.py:466-486 stacks on the host.  out[n,c,y,x] = src_n[y0 + y,
+        x0 + (flip ? Wc-1-x : x), c]; with flip the label's channel 0 is negated; a slot without a mask writes 255.  with_mask False:
+        no mask is written or returned.  out: the four destinations (the last one None without a mask), used as they are."""
+        what = "batch_gather"
+        N = rows.N
+        Hc, Wc = (int(v) for v in crop_shape)
+        shapes = ((N, 3, Hc, Wc), (N, 3, Hc, Wc), (N, 2, Hc, Wc), (N, 1, Hc, Wc))
+        kinds = ("uint8", "uint8", "float32", "uint8")
+        if out is None:
+            dt = (lambda k: getattr(self.ad.torch, k)) if hasattr(self.ad, "torch") else (lambda k: k)
+            out = []
+            for shape, kind in zip(shapes, kinds):
+                if shape[1] == 1 and not with_mask:
+                    out.append(None)
+                    continue
+                nb = N * shape[1] * Hc * Wc * (4 if kind == "float32" else 1)
+                out.append(self.ad.empty_bytes(rows.buf, nb).view(dt(kind))[:nb // (4 if kind == "float32" else 1)].reshape(shape))
+        else:
+            out = list(out)
+            if len(out) != 4:
+                raise ValueError("%s: out must be (img1, img2, label, mask or None)" % what)
+            for o, shape, kind, name in zip(out, shapes, kinds, ("img1", "img2", "label", "mask")):
+                if o is not None:
+                    self._raw(o, "%s: out %s" % (what, name), (kind,), shape)
+                elif name != "mask" or with_mask:
+                    raise ValueError("%s: out %s is missing" % (what, name))
+        i1, i2, lab, msk = out
+        self.check(self.ns.batch_gather(self.ad.ptr(rows.buf), rows.nbytes, rows.tag, N, Hc, Wc, int(bool(with_mask)), self.ad.ptr(i1),
+                                        self.ad.ptr(i2), self.ad.ptr(lab), self.ad.ptr(msk) if with_mask else None,
+                                        self.ad.stream(rows.buf)))
+        return i1, i2, lab, (msk if with_mask else None)
 
     def Upsample_backward(self, out_grad, factor, req="write", out=None):
         """Adjoint of Upsample(factor): (N,C,H*f,W*f) -> (N,C,H,W) (mfn_upsample_bwd)."""
@@ -996,6 +1093,15 @@ class AdamTable:
         return tuple(tuple(r) for r in ptrs) != self.ptrs
 
 
+class BatchRows:
+    """Opaque device table made by OpSet.batch_gather_rows: one 64-byte row per batch slot and the tag that binds it to (N, Hc, Wc).
+    It holds addresses: `samples` keeps the sources alive as long as the table is."""
+
+    def __init__(self, buf, nbytes, tag, N, crop_shape, samples):
+        self.buf, self.nbytes, self.tag, self.N, self.crop_shape = buf, int(nbytes), int(tag), int(N), tuple(crop_shape)
+        self.samples = list(samples)
+
+
 class TorchAdapter:
     """torch-ROCm tensors as device buffers; launches go to torch's current stream."""
 
@@ -1159,6 +1265,14 @@ def multi_adam_table(*a, **k):
 
 def multi_adam_update(*a, **k):
     return default_ops().multi_adam_update(*a, **k)
+
+
+def batch_gather_rows(*a, **k):
+    return default_ops().batch_gather_rows(*a, **k)
+
+
+def batch_gather(*a, **k):
+    return default_ops().batch_gather(*a, **k)
 
 
 def Convolution(*a, **k):

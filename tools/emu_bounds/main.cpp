@@ -53,6 +53,9 @@
 #define mfn_multi_adam_table_bytes mfn_emu_multi_adam_table_bytes
 #define mfn_multi_adam_build_table mfn_emu_multi_adam_build_table
 #define mfn_multi_adam_update mfn_emu_multi_adam_update
+#define mfn_batch_gather_rows_bytes mfn_emu_batch_gather_rows_bytes
+#define mfn_batch_gather_build_rows mfn_emu_batch_gather_build_rows
+#define mfn_batch_gather mfn_emu_batch_gather
 #define mfn_conv2d_out_shape mfn_emu_conv2d_out_shape
 #define mfn_conv2d_workspace_bytes mfn_emu_conv2d_workspace_bytes
 #define mfn_conv2d_packed_weight_bytes mfn_emu_conv2d_packed_weight_bytes
@@ -331,6 +334,49 @@ static void others() {
       snprintf(name, sizeof(name), "multi_adam_update, 8 tensors%s", shift ? ", unaligned" : "");
       report(name, rc ? rc : mfn_multi_adam_update(table.p, need, tag, 8, nb, 1e-4f, 0.9f, 0.999f, 1e-8f, 1e-2f, 0.5f, 1.f, nullptr));
       for (Tensor *t : own) delete t;
+    }
+  }
+  // one training batch out of resident samples (kernels/batch.h): every source array a heap block of exactly its size rounded up to 16 bytes
+  // (the read contract), every output of exactly its size; both store paths, crops on all four source edges, both flips, both label
+  // types, a slot without a mask, a call without one, and a label tensor 12 bytes into its block (single-dword label stores, ends exact)
+  {
+    struct Src { int Hs, Ws, lt, y0, x0, flip, has_mask; };
+    struct Row { const char *name; int Hc, Wc, with_mask, label_off; std::vector<Src> s; };
+    const std::vector<Row> rows = {
+        {"batch_gather 7x10 mixed, byte path", 7, 10, 1, 0, {{9, 14, 0, 0, 0, 0, 1}, {11, 13, 1, 4, 3, 1, 1}, {7, 10, 1, 0, 0, 1, 0}, {8, 23, 0, 1, 13, 0, 1}}},
+        {"batch_gather 7x12 mixed, dword path", 7, 12, 1, 0, {{9, 14, 0, 0, 0, 0, 1}, {11, 13, 1, 4, 1, 1, 1}, {7, 12, 1, 0, 0, 1, 0}, {8, 23, 0, 1, 11, 0, 1}}},
+        {"batch_gather 7x12, label at 12 mod 16", 7, 12, 1, 12, {{9, 14, 0, 2, 2, 1, 1}, {7, 12, 1, 0, 0, 0, 0}}},
+        {"batch_gather 3x5 at the last pixel, no mask", 3, 5, 0, 0, {{5, 9, 0, 2, 4, 1, 1}, {5, 9, 1, 2, 4, 0, 0}}},
+        {"batch_gather 3x260 of 300 at 37", 3, 260, 1, 0, {{4, 300, 0, 1, 37, 0, 1}, {3, 300, 1, 0, 40, 1, 1}}},
+        {"batch_gather 3x261 of 300 at 37", 3, 261, 1, 0, {{4, 300, 1, 1, 37, 1, 1}, {3, 300, 0, 0, 39, 0, 0}}},
+        {"batch_gather 8x16 uncropped", 8, 16, 0, 0, {{8, 16, 0, 0, 0, 0, 0}, {8, 16, 1, 0, 0, 1, 0}}},
+    };
+    for (const Row &r : rows) {
+      const int N = (int)r.s.size();
+      std::vector<Block *> own;
+      auto bytes16 = [&](size_t n) {
+        Block *b = new Block((n + 15) & ~(size_t)15);
+        for (size_t i = 0; i < b->bytes; ++i) ((unsigned char *)b->p)[i] = (unsigned char)(rnd() * 127.f);
+        own.push_back(b);
+        return (const void *)b->p;
+      };
+      std::vector<const void *> i1(N), i2(N), fl(N), mk(N);
+      std::vector<int> Hs(N), Ws(N), lt(N), y0(N), x0(N), flip(N);
+      for (int n = 0; n < N; ++n) {
+        const Src &q = r.s[n];
+        const size_t px = (size_t)q.Hs * q.Ws;
+        i1[n] = bytes16(3 * px); i2[n] = bytes16(3 * px); fl[n] = bytes16((q.lt ? 4 : 8) * px);
+        mk[n] = q.has_mask ? bytes16(px) : nullptr;
+        Hs[n] = q.Hs; Ws[n] = q.Ws; lt[n] = q.lt; y0[n] = q.y0; x0[n] = q.x0; flip[n] = q.flip;
+      }
+      const size_t need = mfn_batch_gather_rows_bytes(N), plane = (size_t)r.Hc * r.Wc;
+      Block table(need), o1(3 * N * plane), o2(3 * N * plane), lab(8 * N * plane + r.label_off), om(r.with_mask ? N * plane : 0);
+      unsigned long long tag = 0;
+      int rc = mfn_batch_gather_build_rows(N, i1.data(), i2.data(), fl.data(), mk.data(), Hs.data(), Ws.data(), lt.data(), y0.data(), x0.data(),
+                                           flip.data(), r.Hc, r.Wc, table.p, need, &tag);
+      report(r.name, rc ? rc : mfn_batch_gather(table.p, need, tag, N, r.Hc, r.Wc, r.with_mask, (unsigned char *)o1.p, (unsigned char *)o2.p,
+                                                (float *)((char *)lab.p + r.label_off), (unsigned char *)om.p, nullptr));
+      for (Block *b : own) delete b;
     }
   }
 }
