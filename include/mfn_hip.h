@@ -422,6 +422,46 @@ int mfn_batch_gather(const void *rows_dev, size_t rows_bytes, unsigned long long
                      unsigned char *img1, unsigned char *img2, float *label, unsigned char *mask, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Raw decoded KITTI / HD1K arrays turned into stored samples -- replaces what the reference's readers do to
+ * every sample at load time on the host with cv2: /root/reference/reader/kitti.py:57-74 and reader/hd1k.py:51-78 (crop, HD1K's
+ * min/max stretch, cv2.resize of the images, bilinear resize of flow and validity, flow re-scaling, the division by the resized
+ * validity, mask quantisation), and cv2.resize of the test images (kitti.py:105-106).  kernels/ingest.h spells out every expression.
+ * Every entry reads a WINDOW (y0, x0, h, w) of an (H, W, 3) array with `pitch` elements per row (pitch >= 3 W).
+ * READ CONTRACT: the array starts at a 16-byte aligned address and is readable up to the next multiple of 16 bytes of its size;
+ * nothing outside that extent is touched.  Outputs are dense and 16-byte aligned.
+ * The resampling is OpenCV's INTER_LINEAR (half-pixel centres, edge replicate, no antialiasing) restated from its generic path; its
+ * positions and coefficients come from tables that the host-only entry below fills in a caller-owned HOST buffer (8-byte aligned,
+ * 32 bytes per destination column and row) for one (window size, destination size); the caller uploads the bytes as they are
+ * (16-byte aligned on the device), once per pair of sizes.  The tag binds the tables to the four sizes; an entry refuses tables
+ * whose byte count or tag does not fit its own sizes (MFN_E_SHAPE).
+ * Errors before any launch: a NULL array, output or table (MFN_E_NULL); a size < 1, a pitch below 3 W, a window that leaves its
+ * array, a flow window with a side < 2 -- the reference's flow scale is x / 0 there -- (MFN_E_SHAPE); an address that is not
+ * aligned as stated (MFN_E_ALIGN); bgr, premultiply or flow_type outside their values (MFN_E_PARAM). */
+size_t mfn_ingest_tables_bytes(int dst_h, int dst_w);
+int mfn_ingest_build_tables(int src_h, int src_w, int dst_h, int dst_w, void *tables_host, size_t tables_bytes,
+                            unsigned long long *tag);
+/* hd1k.py:55: minmax[0] = the minimum, minmax[1] = the maximum over both windows, all channels.  Two launches (the words' initial
+ * values, then per-block reductions folded in with vector atomicMin / atomicMax): no workspace, no synchronisation. */
+int mfn_ingest_minmax(const unsigned char *img1, const unsigned char *img2, int H, int W, long long pitch, int y0, int x0, int h,
+                      int w, unsigned *minmax, void *stream);
+/* uint8 window -> dst (dst_h, dst_w, 3) uint8: the channels reversed with bgr != 0 (cv2.imread's order, kitti.py:54), then with
+ * minmax_or_null != NULL hd1k.py:56's stretch uint8((v - min) * (255.0 / (max - min))) in double (min == max, where the reference
+ * divides by zero, gives 0), then cv2.resize's fixed-point bilinear (kitti.py:66).  At equal sizes: the source bytes. */
+int mfn_ingest_image(const unsigned char *src, int H, int W, long long pitch, int y0, int x0, int h, int w, const void *tables_dev,
+                     size_t tables_bytes, unsigned long long tag, int bgr, const unsigned *minmax_or_null, unsigned char *dst,
+                     int dst_h, int dst_w, void *stream);
+/* uint16 window in the file's channel order (R = u, G = v, B = valid) -> flow (dst_h, dst_w, 2) in (u, v) order, fp32
+ * (flow_type 0) or fp16 (1: round to nearest even), and mask (dst_h, dst_w, 1) uint8: kitti.py:61-72, with premultiply != 0
+ * hd1k.py:57-76.  At equal sizes the readers' resize=None branch. */
+int mfn_ingest_flow_occ(const unsigned short *src, int H, int W, long long pitch, int y0, int x0, int h, int w,
+                        const void *tables_dev, size_t tables_bytes, unsigned long long tag, int premultiply, int flow_type,
+                        void *flow, unsigned char *mask, int dst_h, int dst_w, void *stream);
+/* Host code, no GPU: reverses the five row filters of a PNG image in place (what cv2.imread of kitti.py:54-56 and skimage.io.imread
+ * of reader/sintel.py:79 do inside libpng).  raw: `rows` scanlines of 1 + row_bytes bytes as inflated, the filter type first;
+ * bytes_per_pixel: 1..8.  A filter type above 4: MFN_E_PARAM. */
+int mfn_png_unfilter(unsigned char *raw, long long rows, long long row_bytes, int bytes_per_pixel);
+
+/* ---------------------------------------------------------------------------------------------
  * Convolution / Deconvolution -- replace the Gluon blocks of
  * /root/reference/network/MaskFlownet.py:79-163: nn.Conv2D(channels, kernel_size=3, strides, padding, dilation)
  * [+ LeakyReLU(0.1)] of conv() / predict_flow() / predict_mask() (:165-191) and nn.Conv2DTranspose(channels, 4, 2, 1)

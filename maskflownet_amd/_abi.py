@@ -77,6 +77,13 @@ SIGNATURES = {
     "batch_gather_rows_bytes": (C.c_size_t, [_i]),
     "batch_gather_build_rows": (_i, [_i] + [C.POINTER(C.c_void_p)] * 4 + [_pi] * 6 + [_i, _i, C.c_void_p, C.c_size_t, C.POINTER(C.c_ulonglong)]),
     "batch_gather": (_i, [C.c_void_p, C.c_size_t, C.c_ulonglong] + [_i] * 4 + [C.c_void_p] * 4 + [_s]),
+    # raw decoded arrays into stored samples (kernels/ingest.h); the tables entries and png_unfilter are host-only
+    "ingest_tables_bytes": (C.c_size_t, [_i, _i]),
+    "ingest_build_tables": (_i, [_i] * 4 + [C.c_void_p, C.c_size_t, C.POINTER(C.c_ulonglong)]),
+    "ingest_minmax": (_i, [C.c_void_p, C.c_void_p, _i, _i, C.c_longlong] + [_i] * 4 + [C.c_void_p, _s]),
+    "ingest_image": (_i, [C.c_void_p, _i, _i, C.c_longlong] + [_i] * 4 + [C.c_void_p, C.c_size_t, C.c_ulonglong, _i, C.c_void_p, C.c_void_p, _i, _i, _s]),
+    "ingest_flow_occ": (_i, [C.c_void_p, _i, _i, C.c_longlong] + [_i] * 4 + [C.c_void_p, C.c_size_t, C.c_ulonglong, _i, _i, C.c_void_p, C.c_void_p, _i, _i, _s]),
+    "png_unfilter": (_i, [C.c_void_p, C.c_longlong, C.c_longlong, _i]),
     "set_arithmetic": (_i, [C.c_char_p, _i]),
     "get_arithmetic": (_i, [C.c_char_p, _pi]),
     "set_tuning": (_i, [C.c_char_p, _i]),

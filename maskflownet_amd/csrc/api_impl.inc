@@ -23,6 +23,7 @@
 #include "kernels/loss.h"
 #include "kernels/optimizer.h"
 #include "kernels/batch.h"
+#include "kernels/ingest.h"
 #include "kernels/backward.h"
 #include "kernels/dc_backward.h"
 #include "kernels/conv.h"
@@ -2003,6 +2004,105 @@ int MFN_API(batch_gather)(const void *rows_dev, size_t rows_bytes, unsigned long
   p.N = N; p.Hc = Hc; p.Wc = Wc;
   p.label16 = aligned(label, 16) ? 1u : 0u;
   return hipfail(batch_gather_launch(p, (hipStream_t)stream), "batch_gather");
+}
+
+// ---- raw decoded arrays into stored samples (kernels/ingest.h) -------------------------------------------------------------------
+size_t MFN_API(ingest_tables_bytes)(int dst_h, int dst_w) { return ingest_tables_bytes(dst_h, dst_w); }
+
+int MFN_API(ingest_build_tables)(int src_h, int src_w, int dst_h, int dst_w, void *tables_host, size_t tables_bytes,
+                                 unsigned long long *tag) {
+  const char *what = "ingest_build_tables";
+  if (src_h < 1 || src_w < 1 || dst_h < 1 || dst_w < 1) return fail(MFN_E_SHAPE, "%s: source %dx%d, destination %dx%d", what, src_h, src_w, dst_h, dst_w);
+  if (!tables_host || !tag) return fail(MFN_E_NULL, "%s: NULL output (tables_host, tag)", what);
+  if (tables_bytes < ingest_tables_bytes(dst_h, dst_w))
+    return fail(MFN_E_SHAPE, "%s: tables of %zu bytes needed, %zu given", what, ingest_tables_bytes(dst_h, dst_w), tables_bytes);
+  if (!aligned(tables_host, 8)) return fail(MFN_E_ALIGN, "%s: the tables must be 8-byte aligned", what);
+  ingest_build_tables((IngestTap *)tables_host, src_h, src_w, dst_h, dst_w);
+  *tag = ingest_tables_tag(src_h, src_w, dst_h, dst_w);
+  return 0;
+}
+
+// The window (y0, x0, h, w) of an (H, W, 3) array with `pitch` elements per row: sizes, pitch, the window inside the array.
+static int ingest_window(const char *what, int H, int W, long long pitch, int y0, int x0, int h, int w, int min_side) {
+  if (H < 1 || W < 1 || h < 1 || w < 1) return fail(MFN_E_SHAPE, "%s: array %dx%d, window %dx%d", what, H, W, h, w);
+  if (pitch < 3ll * W) return fail(MFN_E_SHAPE, "%s: a pitch of %lld elements is less than a row of %d pixels (%lld)", what, pitch, W, 3ll * W);
+  if (y0 < 0 || x0 < 0 || (long long)y0 + h > H || (long long)x0 + w > W)
+    return fail(MFN_E_SHAPE, "%s: the window %dx%d at (%d, %d) leaves the %dx%d array", what, h, w, y0, x0, H, W);
+  if (h < min_side || w < min_side) return fail(MFN_E_SHAPE, "%s: a window of %dx%d: both sides must be at least %d", what, h, w, min_side);
+  if ((long long)H * pitch > 0x7FFFFFFFll) return fail(MFN_E_UNSUPPORTED, "%s: an array of %d rows of %lld elements is too large", what, H, pitch);
+  return 0;
+}
+static int ingest_tables_ok(const char *what, const void *tables, size_t bytes, unsigned long long tag, int h, int w, int dst_h, int dst_w) {
+  if (dst_h < 1 || dst_w < 1) return fail(MFN_E_SHAPE, "%s: destination %dx%d", what, dst_h, dst_w);
+  if ((long long)dst_h * dst_w > 0x1FFFFFFFll) return fail(MFN_E_UNSUPPORTED, "%s: a destination of %dx%d is more than one launch covers", what, dst_h, dst_w);
+  if (!tables) return fail(MFN_E_NULL, "%s: NULL tables", what);
+  if (bytes != ingest_tables_bytes(dst_h, dst_w))
+    return fail(MFN_E_SHAPE, "%s: tables of %zu bytes expected for a %dx%d destination, %zu given", what, ingest_tables_bytes(dst_h, dst_w), dst_h, dst_w, bytes);
+  if (tag != ingest_tables_tag(h, w, dst_h, dst_w))
+    return fail(MFN_E_SHAPE, "%s: the tables (tag %llx) were not built for a %dx%d window and a %dx%d destination: re-run mfn_ingest_build_tables", what, tag,
+                h, w, dst_h, dst_w);
+  if (!aligned(tables, 16)) return fail(MFN_E_ALIGN, "%s: the tables must be 16-byte aligned", what);
+  return 0;
+}
+
+int MFN_API(ingest_minmax)(const unsigned char *img1, const unsigned char *img2, int H, int W, long long pitch, int y0, int x0, int h,
+                           int w, unsigned *minmax, void *stream) {
+  const char *what = "ingest_minmax";
+  if (!img1 || !img2 || !minmax) return fail(MFN_E_NULL, "%s: NULL array or output", what);
+  if (int rc = ingest_window(what, H, W, pitch, y0, x0, h, w, 1)) return rc;
+  if (!aligned(img1, 16) || !aligned(img2, 16)) return fail(MFN_E_ALIGN, "%s: the arrays must be 16-byte aligned", what);
+  if (!aligned(minmax, 4)) return fail(MFN_E_ALIGN, "%s: the output must be 4-byte aligned", what);
+  IngestMinmaxParams p{};
+  p.img1 = img1; p.img2 = img2; p.pitch = pitch; p.y0 = y0; p.x0 = x0; p.h = h; p.w = w; p.out = minmax;
+  return hipfail(ingest_minmax_launch(p, (hipStream_t)stream), what);
+}
+
+int MFN_API(ingest_image)(const unsigned char *src, int H, int W, long long pitch, int y0, int x0, int h, int w, const void *tables_dev,
+                          size_t tables_bytes, unsigned long long tag, int bgr, const unsigned *minmax_or_null, unsigned char *dst,
+                          int dst_h, int dst_w, void *stream) {
+  const char *what = "ingest_image";
+  if (!src || !dst) return fail(MFN_E_NULL, "%s: NULL array or output", what);
+  if (int rc = ingest_window(what, H, W, pitch, y0, x0, h, w, 1)) return rc;
+  if (int rc = ingest_tables_ok(what, tables_dev, tables_bytes, tag, h, w, dst_h, dst_w)) return rc;
+  if (bgr != 0 && bgr != 1) return fail(MFN_E_PARAM, "%s: bgr %d (0 or 1)", what, bgr);
+  if (!aligned(src, 16) || !aligned(dst, 16)) return fail(MFN_E_ALIGN, "%s: the array and the output must be 16-byte aligned", what);
+  if (!aligned(minmax_or_null, 4)) return fail(MFN_E_ALIGN, "%s: the min/max words must be 4-byte aligned", what);
+  IngestImageParams p{};
+  p.src = src + (long long)y0 * pitch + 3ll * x0;
+  p.pitch = pitch;
+  p.cols = (const IngestTap *)tables_dev; p.rows = p.cols + dst_w;
+  p.minmax = minmax_or_null; p.dst = dst; p.Hd = dst_h; p.Wd = dst_w; p.bgr = (unsigned)bgr;
+  return hipfail(ingest_image_launch(p, (hipStream_t)stream), what);
+}
+
+int MFN_API(ingest_flow_occ)(const unsigned short *src, int H, int W, long long pitch, int y0, int x0, int h, int w,
+                             const void *tables_dev, size_t tables_bytes, unsigned long long tag, int premultiply, int flow_type,
+                             void *flow, unsigned char *mask, int dst_h, int dst_w, void *stream) {
+  const char *what = "ingest_flow_occ";
+  if (!src || !flow || !mask) return fail(MFN_E_NULL, "%s: NULL array or output", what);
+  if (int rc = ingest_window(what, H, W, pitch, y0, x0, h, w, 2)) return rc;
+  if (int rc = ingest_tables_ok(what, tables_dev, tables_bytes, tag, h, w, dst_h, dst_w)) return rc;
+  if (premultiply != 0 && premultiply != 1) return fail(MFN_E_PARAM, "%s: premultiply %d (0 or 1)", what, premultiply);
+  if (flow_type != INGEST_FLOW_F32 && flow_type != INGEST_FLOW_F16) return fail(MFN_E_PARAM, "%s: flow type %d (0 = fp32, 1 = fp16)", what, flow_type);
+  if (!aligned(src, 16) || !aligned(flow, 16) || !aligned(mask, 16)) return fail(MFN_E_ALIGN, "%s: the array and the outputs must be 16-byte aligned", what);
+  IngestFlowParams p{};
+  p.src = src + (long long)y0 * pitch + 3ll * x0;
+  p.pitch = pitch;
+  p.cols = (const IngestTap *)tables_dev; p.rows = p.cols + dst_w;
+  p.flow = flow; p.mask = mask; p.Hd = dst_h; p.Wd = dst_w;
+  p.premultiply = (unsigned)premultiply; p.flow_type = (unsigned)flow_type;
+  p.sx = (float)(dst_w - 1) / (float)(w - 1);
+  p.sy = (float)(dst_h - 1) / (float)(h - 1);
+  return hipfail(ingest_flow_occ_launch(p, (hipStream_t)stream), what);
+}
+
+int MFN_API(png_unfilter)(unsigned char *raw, long long rows, long long row_bytes, int bytes_per_pixel) {
+  if (rows < 0 || row_bytes < 0 || bytes_per_pixel < 1 || bytes_per_pixel > 8)
+    return fail(MFN_E_SHAPE, "png_unfilter: rows=%lld row_bytes=%lld bytes_per_pixel=%d", rows, row_bytes, bytes_per_pixel);
+  if (rows != 0 && !raw) return fail(MFN_E_NULL, "png_unfilter: NULL buffer");
+  const long long bad = png_unfilter(raw, rows, row_bytes, bytes_per_pixel);
+  if (bad) return fail(MFN_E_PARAM, "png_unfilter: row %lld has a filter type that is none of 0..4", bad - 1);
+  return 0;
 }
 
 int MFN_API(leaky_relu_bwd)(const float *gout, const float *y, float *gin, size_t n, float slope, void *stream) {

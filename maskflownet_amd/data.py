@@ -11,6 +11,14 @@ writes the bytes `batch_samples` would have stacked.  The result is what `traini
     feed = data.Feeder(data.BatchSampler([ds] * 8, (384, 512), seed=0))
     img1, img2, label, mask = feed.next()
 
+KITTI and HD1K are not stored as read: the reference's readers crop, stretch, resize and normalise every sample with cv2 at load time
+(reader/kitti.py:57-74, reader/hd1k.py:51-78).  `DeviceDataset.append_raw` takes the decoded files as they are (readers.py) and runs
+that stage on the device, straight into the arena (kernels/ingest.h):
+
+    kitti = data.DeviceDataset("cuda")
+    for a, b, fo in readers.kitti_samples(image_dir, flow_dir, indices):
+        kitti.append_raw(a, b, fo, crop=(370, 1224))         # main.py:325's kitti.read_dataset(..., crop = (370, 1224))
+
 All randomness is the sampler's: a batch is a function of (seed, step), and `BatchSampler.state()` / `set_state()` continue a run
 where a checkpoint left it.
 """
@@ -46,6 +54,7 @@ class DeviceDataset:
         self._chunks, self._used = [], 0
         self._samples = []            # (img1, img2, flow, mask or None): views into the chunks
         self._stage, self._staged = None, None
+        self._raw, self._minmax = None, None      # append_raw: the uploaded raw arrays (reused), HD1K's min / max words
         self._nbytes = 0
 
     # ---- the arena ---------------------------------------------------------------------------------------------------------
@@ -111,6 +120,89 @@ class DeviceDataset:
         self.has_mask = mask is not None
         self._samples.append(tuple(views) if mask is not None else (views[0], views[1], views[2], None))
         self._nbytes += total
+        return len(self._samples) - 1
+
+    @staticmethod
+    def _window(H, W, crop):
+        """(y0, x0, h, w) of the readers' crops: (h, w) = the bottom h rows and the left w columns (kitti.py:57-60);
+        ((top, bottom), (left, right)) = margins (hd1k.py:51)."""
+        if crop is None:
+            return 0, 0, H, W
+        if isinstance(crop[0], (tuple, list)):
+            (t, b), (l, r) = ((int(v) for v in side) for side in crop)
+            win = (t, l, H - t - b, W - l - r)
+            if min(t, b, l, r) < 0:
+                raise ValueError("DeviceDataset.append_raw: negative crop margins %s" % (crop,))
+        else:
+            h, w = (int(v) for v in crop)
+            win = (H - h, 0, h, w)
+        if win[0] < 0 or win[2] < 1 or win[3] < 1 or win[1] + win[3] > W:
+            raise ValueError("DeviceDataset.append_raw: crop %s does not fit a %dx%d sample" % (crop, H, W))
+        return win
+
+    def append_raw(self, img1, img2, flow_occ_u16, *, crop=None, resize=None, bgr=True, premultiply=False, normalize=False):
+        """One KITTI / HD1K sample from its decoded files (io.read_png: RGB order): img1, img2 uint8 (H,W,3), flow_occ_u16 uint16
+        (H,W,3) with R = u, G = v, B = valid.  What the reference's readers do on the host with cv2 runs here on the device, from
+        the uploaded raw arrays straight into the stored sample (kernels/ingest.h): crop -- (h, w): the bottom h rows and the left w
+        columns (kitti.py:57-60); ((top, bottom), (left, right)): margins (hd1k.py:51) --, channel reversal to cv2.imread's BGR
+        (bgr), HD1K's min/max stretch of both images (normalize, hd1k.py:54-56), cv2.resize to resize = (W', H') (None: the window's
+        size), the flow's re-scaling and its division by the resized validity, with HD1K's multiplication by the validity first
+        (premultiply, hd1k.py:60), and the mask uint8(validity * 255).  The flow is stored in the data set's flow_dtype.  -> its index."""
+        img1, img2, fo = (np.ascontiguousarray(a) for a in (img1, img2, flow_occ_u16))
+        if img1.dtype != np.uint8 or img1.ndim != 3 or img1.shape[2] != 3 or min(img1.shape[:2]) < 1:
+            raise ValueError("DeviceDataset.append_raw: img1 must be uint8 (H, W, 3), got %s %s" % (img1.dtype, img1.shape))
+        H, W = img1.shape[:2]
+        if img2.dtype != np.uint8 or img2.shape != (H, W, 3):
+            raise ValueError("DeviceDataset.append_raw: img2 must be uint8 %s, got %s %s" % ((H, W, 3), img2.dtype, img2.shape))
+        if fo.dtype != np.uint16 or fo.shape != (H, W, 3):
+            raise ValueError("DeviceDataset.append_raw: flow_occ_u16 must be uint16 %s, got %s %s" % ((H, W, 3), fo.dtype, fo.shape))
+        if self.has_mask is False:
+            raise ValueError("DeviceDataset.append_raw: this data set has no masks")
+        win = self._window(H, W, crop)
+        if min(win[2:]) < 2:
+            raise ValueError("DeviceDataset.append_raw: a window of %dx%d: both sides must be at least 2" % win[2:])
+        Hd, Wd = (win[2], win[3]) if resize is None else (int(resize[1]), int(resize[0]))
+        if min(Hd, Wd) < 1:
+            raise ValueError("DeviceDataset.append_raw: resize %s" % (resize,))
+        # the raw arrays: pinned staging, one copy into a reused device buffer (kernels of the previous call are ahead on the stream)
+        offs, total = [], 0
+        for a in (img1, img2, fo):
+            offs.append(total)
+            total += _pad16(a.nbytes)
+        stage = self._staging(total)
+        host = stage.numpy()
+        for a, o in zip((img1, img2, fo), offs):
+            host[o:o + a.nbytes] = a.reshape(-1).view(np.uint8)
+        if self._raw is None or self._raw.numel() < total:
+            self._raw = torch.empty(total, dtype=torch.uint8, device=self.device)
+        self._raw[:total].copy_(stage[:total], non_blocking=True)
+        self._staged = torch.cuda.Event()
+        self._staged.record(torch.cuda.current_stream(self.device))
+        r1, r2 = (self._raw[o:o + img1.nbytes].view(H, W, 3) for o in offs[:2])
+        rf = self._raw[offs[2]:offs[2] + fo.nbytes].view(torch.uint16).view(H, W, 3)
+        # the stored sample: two images, the flow, the mask at the destination size
+        np_flow, torch_flow = _FLOW[self.flow_dtype]
+        sizes = [Hd * Wd * 3, Hd * Wd * 3, Hd * Wd * 2 * np.dtype(np_flow).itemsize, Hd * Wd]
+        starts, need = [], 0
+        for n in sizes:
+            starts.append(need)
+            need += _pad16(n)
+        chunk, base = self._reserve(need)
+        parts = [chunk[base + o:base + o + n] for o, n in zip(starts, sizes)]
+        v1, v2 = parts[0].view(Hd, Wd, 3), parts[1].view(Hd, Wd, 3)
+        vf, vm = parts[2].view(torch_flow).view(Hd, Wd, 2), parts[3].view(Hd, Wd, 1)
+        tables = ops.ingest_tables(win[2:], (Hd, Wd), like=chunk)
+        mm = None
+        if normalize:
+            if self._minmax is None:
+                self._minmax = torch.empty(2, dtype=torch.int32, device=self.device)
+            mm = ops.ingest_minmax(r1, r2, win, out=self._minmax)
+        ops.ingest_image(r1, win, (Hd, Wd), tables, bgr=bgr, minmax=mm, out=v1)
+        ops.ingest_image(r2, win, (Hd, Wd), tables, bgr=bgr, minmax=mm, out=v2)
+        ops.ingest_flow_occ(rf, win, (Hd, Wd), tables, premultiply=premultiply, flow_dtype=self.flow_dtype, out_flow=vf, out_mask=vm)
+        self.has_mask = True
+        self._samples.append((v1, v2, vf, vm))
+        self._nbytes += need
         return len(self._samples) - 1
 
     def extend(self, samples):

@@ -15,8 +15,18 @@
   weights are absent (.MISSING_LARGE_BLOBS), so the reader is pinned by tests/golden/mxnet_v2.params -- assembled byte
   by byte from that layout by tests/golden/make_params_fixture.py, independently of the writer below -- and by round
   trips.
+* PNG, the frames of Sintel / KITTI / HD1K, Sintel's invalid masks and KITTI's 16-bit flow maps (cv2.imread of
+  /root/reference/reader/kitti.py:54-56 and reader/hd1k.py:51-53, skimage.io.imread of reader/sintel.py:79): the
+  8-byte signature, then chunks of uint32 length, 4-byte type, data, CRC-32 of type and data, all big endian.  IHDR:
+  width, height, bit depth, colour type (0 gray, 2 RGB, 3 palette, 4 gray + alpha, 6 RGBA), compression, filter,
+  interlace.  The IDAT chunks together are one zlib stream of scanlines, each a filter-type byte (None, Sub, Up,
+  Average, Paeth) followed by the filtered bytes; 16-bit samples are big endian.  Restated from the PNG specification
+  on `zlib` alone; the filters are reversed by mfn_png_unfilter, host C++ inside the library.  `read_png` returns the
+  FILE's channel order (RGB), not cv2's BGR.  `write_kitti_flow` is the benchmark submission writer of
+  /root/reference/predict.py:63-66.
 """
 import struct
+import zlib
 
 import numpy as np
 
@@ -77,6 +87,97 @@ def read_ppm(path):
     if len(buf) - pos < 3 * w * h:
         raise ValueError("%s: truncated PPM payload (%d of %d bytes)" % (path, max(0, len(buf) - pos), 3 * w * h))
     return np.frombuffer(buf, np.uint8, 3 * w * h, pos).reshape(h, w, 3).copy()
+
+
+_PNG_SIG = b"\x89PNG\r\n\x1a\n"
+_PNG_CHANNELS = {0: 1, 2: 3, 4: 2, 6: 4}
+
+
+def read_png(path):
+    """-> (H, W) for gray, (H, W, C) otherwise, uint8 or uint16, in the file's channel order.  Colour types 0, 2, 4, 6 at bit
+    depths 8 and 16, all five row filters, any number of IDAT chunks; interlaced and palette files raise."""
+    with open(path, "rb") as f:
+        buf = f.read()
+    if buf[:8] != _PNG_SIG:
+        raise ValueError("%s: not a PNG file (signature %r)" % (path, buf[:8]))
+    pos, head, idat, ended = 8, None, [], False
+    while pos + 12 <= len(buf) and not ended:
+        (n,) = struct.unpack_from(">I", buf, pos)
+        kind, data = buf[pos + 4:pos + 8], buf[pos + 8:pos + 8 + n]
+        if len(data) != n or pos + 12 + n > len(buf):
+            raise ValueError("%s: truncated %r chunk" % (path, kind))
+        if struct.unpack_from(">I", buf, pos + 8 + n)[0] != (zlib.crc32(kind + data) & 0xFFFFFFFF):
+            raise ValueError("%s: bad CRC of a %r chunk" % (path, kind))
+        pos += 12 + n
+        if kind == b"IHDR":
+            head = struct.unpack(">IIBBBBB", data)
+        elif kind == b"IDAT":
+            idat.append(data)
+        elif kind == b"IEND":
+            ended = True
+    if head is None or not idat or not ended:
+        raise ValueError("%s: a PNG file needs IHDR, IDAT and IEND chunks" % path)
+    w, h, depth, ctype, comp, filt, lace = head
+    if w <= 0 or h <= 0 or w > 99999 or h > 99999:
+        raise ValueError("%s: implausible PNG size %dx%d" % (path, w, h))
+    if ctype == 3:
+        raise ValueError("%s: palette PNG files are not read" % path)
+    if lace != 0:
+        raise ValueError("%s: interlaced PNG files are not read" % path)
+    if ctype not in _PNG_CHANNELS or depth not in (8, 16) or comp != 0 or filt != 0:
+        raise ValueError("%s: PNG colour type %d at bit depth %d (compression %d, filter %d) is not read" % (path, ctype, depth, comp, filt))
+    C, item = _PNG_CHANNELS[ctype], depth // 8
+    row = w * C * item
+    raw = np.frombuffer(zlib.decompress(b"".join(idat)), np.uint8)
+    if raw.size != h * (row + 1):
+        raise ValueError("%s: %d bytes of image data, %d expected" % (path, raw.size, h * (row + 1)))
+    raw = raw.copy()
+    from . import _lib
+    _lib.check(_lib.lib().png_unfilter(raw.ctypes.data, h, row, C * item), "png_unfilter")
+    px = np.ascontiguousarray(raw.reshape(h, row + 1)[:, 1:])
+    out = px if item == 1 else px.view(">u2").astype(np.uint16)
+    return out.reshape((h, w) if C == 1 else (h, w, C))
+
+
+def _png_chunk(kind, data):
+    return struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(kind + data) & 0xFFFFFFFF)
+
+
+def write_png(path, array):
+    """8-bit or 16-bit gray (H, W), gray + alpha (H, W, 2), RGB (H, W, 3) or RGBA (H, W, 4); filter None, one IDAT."""
+    a = np.asarray(array)
+    if a.dtype not in (np.uint8, np.uint16) or a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] not in (1, 2, 3, 4)) or min(a.shape[:2]) < 1:
+        raise ValueError("write_png: expected uint8 or uint16 (H, W) or (H, W, 1..4), got %s %s" % (a.dtype, a.shape))
+    h, w = a.shape[:2]
+    C = 1 if a.ndim == 2 else a.shape[2]
+    ctype = {1: 0, 2: 4, 3: 2, 4: 6}[C]
+    rows = np.ascontiguousarray(a.reshape(h, w * C).astype(">u2" if a.dtype == np.uint16 else np.uint8)).view(np.uint8).reshape(h, -1)
+    raw = np.zeros((h, rows.shape[1] + 1), np.uint8)
+    raw[:, 1:] = rows
+    with open(path, "wb") as f:
+        f.write(_PNG_SIG + _png_chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8 * a.dtype.itemsize, ctype, 0, 0, 0))
+                + _png_chunk(b"IDAT", zlib.compress(raw.tobytes(), 6)) + _png_chunk(b"IEND", b""))
+
+
+def write_kitti_flow(path, flow_hw2_uv):
+    """KITTI's 16-bit flow map of a prediction, (H, W, 2) in (u, v) order (predict.py:63-66): R = uint16(64.0 * (u + 512)), G the
+    same of v, both evaluated in float64 and truncated, B = 1 (numpy evaluates the reference's expression in float32 for a float32
+    flow, which can round u + 512 before the truncation; float64 is the exact quantisation).  Values outside the format's range
+    (-512 .. 511.98) saturate."""
+    fl = np.asarray(flow_hw2_uv, np.float64)
+    if fl.ndim != 3 or fl.shape[2] != 2:
+        raise ValueError("write_kitti_flow: expected (H, W, 2), got %s" % (fl.shape,))
+    pred = np.ones(fl.shape[:2] + (3,), np.uint16)
+    pred[..., 0:2] = np.clip(64.0 * (fl + 512.0), 0.0, 65535.0).astype(np.uint16)
+    write_png(path, pred)
+
+
+def read_sintel_invalid(path):
+    """Sintel's invalid map as the reference's mask (reader/sintel.py:80-81): 255 - gray[..., None], uint8 (H, W, 1)."""
+    gray = read_png(path)
+    if gray.ndim != 2 or gray.dtype != np.uint8:
+        raise ValueError("%s: an 8-bit gray PNG expected, got %s %s" % (path, gray.dtype, gray.shape))
+    return 255 - gray[..., None]
 
 
 def write_flo(path, flow_hw2):

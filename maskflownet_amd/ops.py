@@ -824,6 +824,101 @@ class OpSet:
                                         self.ad.stream(rows.buf)))
         return i1, i2, lab, (msk if with_mask else None)
 
+    # ---- raw decoded KITTI / HD1K arrays into stored samples (reader/kitti.py:57-74, reader/hd1k.py:51-78) ---------------------------
+    _INGEST_FLOW = {"float32": 0, "float16": 1}
+
+    def _like(self, like):
+        """A device array to allocate next to: `like`, or (torch) an empty tensor on the current ROCm device."""
+        if like is None and hasattr(self.ad, "torch"):
+            like = self.ad.torch.empty(0, device="cuda")
+        return like
+
+    def _raw_out(self, like, shape, kind, out, what):
+        """The destination of an ingest op: `out` as it is (dtype, shape and density checked), or a fresh dense array."""
+        if out is not None:
+            self._raw(out, what, (kind,), shape)
+            return out
+        item = {"uint8": 1, "int32": 4, "float32": 4, "float16": 2}[kind]
+        n = 1
+        for d in shape:
+            n *= int(d)
+        dt = getattr(self.ad.torch, kind) if hasattr(self.ad, "torch") else kind
+        return self.ad.empty_bytes(like, max(n * item, 4)).view(dt)[:n].reshape(tuple(shape))
+
+    def ingest_tables(self, src_hw, dst_hw, like=None):
+        """The device-resident resampling tables of mfn_ingest_image / mfn_ingest_flow_occ for a (h, w) window and a (H', W')
+        destination: OpenCV's INTER_LINEAR positions and coefficients per destination column and row, built on the host by
+        mfn_ingest_build_tables, uploaded once and cached per pair of sizes (and device / stream)."""
+        h, w = (int(v) for v in src_hw)
+        Hd, Wd = (int(v) for v in dst_hw)
+        like = self._like(like)
+        key = (h, w, Hd, Wd, self.ad.device_key(like))
+        if not hasattr(self, "_ingest_cache"):
+            self._ingest_cache = {}
+        tab = self._ingest_cache.get(key)
+        if tab is None:
+            nbytes = self.ns.ingest_tables_bytes(Hd, Wd)
+            host = (ctypes.c_ulonglong * max(1, nbytes // 8))()
+            tag = ctypes.c_ulonglong()
+            self.check(self.ns.ingest_build_tables(h, w, Hd, Wd, ctypes.addressof(host), nbytes, ctypes.byref(tag)))
+            tab = IngestTables(self._upload(like, host, nbytes), nbytes, tag.value, (h, w), (Hd, Wd))
+            self._ingest_cache[key] = tab
+        return tab
+
+    def _ingest_src(self, src, window, kind, what):
+        self._raw(src, what, (kind,))
+        shp = self.ad.shape(src)
+        if len(shp) != 3 or shp[2] != 3:
+            raise ValueError("%s has shape %s, expected (H, W, 3)" % (what, shp))
+        y0, x0, h, w = ((0, 0, shp[0], shp[1]) if window is None else (int(v) for v in window))
+        return int(shp[0]), int(shp[1]), y0, x0, h, w
+
+    def ingest_minmax(self, img1, img2, window=None, out=None):
+        """min and max over the window (y0, x0, h, w) of both uint8 (H, W, 3) images, all channels (hd1k.py:55) -> int32 (2,) on the
+        device (mfn_ingest_minmax); what ingest_image's `minmax` takes."""
+        what = "ingest_minmax"
+        H, W, y0, x0, h, w = self._ingest_src(img1, window, "uint8", what + ": img1")
+        self._raw(img2, what + ": img2", ("uint8",), (H, W, 3))
+        out = self._raw_out(img1, (2,), "int32", out, what + ": out")
+        self.check(self.ns.ingest_minmax(self.ad.ptr(img1), self.ad.ptr(img2), H, W, 3 * W, y0, x0, h, w, self.ad.ptr(out), self.ad.stream(img1)))
+        return out
+
+    def ingest_image(self, src, window, dst_hw, tables, bgr=False, minmax=None, out=None):
+        """The window (y0, x0, h, w) of a uint8 (H, W, 3) device array -> uint8 (H', W', 3): channel reversal (bgr), HD1K's contrast
+        stretch (minmax: ingest_minmax's result), cv2.resize's fixed-point bilinear (mfn_ingest_image).  tables: ingest_tables((h, w),
+        (H', W')).  The source must be readable up to the next multiple of 16 bytes of its size."""
+        what = "ingest_image"
+        H, W, y0, x0, h, w = self._ingest_src(src, window, "uint8", what + ": src")
+        Hd, Wd = (int(v) for v in dst_hw)
+        if minmax is not None:
+            self._raw(minmax, what + ": minmax", ("int32",), (2,))
+        out = self._raw_out(src, (Hd, Wd, 3), "uint8", out, what + ": out")
+        self.check(self.ns.ingest_image(self.ad.ptr(src), H, W, 3 * W, y0, x0, h, w, self.ad.ptr(tables.buf), tables.nbytes, tables.tag, int(bool(bgr)),
+                                        None if minmax is None else self.ad.ptr(minmax), self.ad.ptr(out), Hd, Wd, self.ad.stream(src)))
+        return out
+
+    def ingest_flow_occ(self, src_u16, window, dst_hw, tables, premultiply=False, flow_dtype="float32", out_flow=None, out_mask=None):
+        """The window of a uint16 (H, W, 3) device array in the file's order (R = u, G = v, B = valid) -> (flow (H', W', 2) in (u, v)
+        order, float32 or float16; mask (H', W', 1) uint8): kitti.py:61-72, with premultiply hd1k.py:57-76 (mfn_ingest_flow_occ)."""
+        what = "ingest_flow_occ"
+        if flow_dtype not in self._INGEST_FLOW:
+            raise ValueError("%s: flow_dtype must be 'float32' or 'float16', got %r" % (what, flow_dtype))
+        H, W, y0, x0, h, w = self._ingest_src(src_u16, window, "uint16", what + ": src")
+        Hd, Wd = (int(v) for v in dst_hw)
+        out_flow = self._raw_out(src_u16, (Hd, Wd, 2), flow_dtype, out_flow, what + ": out_flow")
+        out_mask = self._raw_out(src_u16, (Hd, Wd, 1), "uint8", out_mask, what + ": out_mask")
+        self.check(self.ns.ingest_flow_occ(self.ad.ptr(src_u16), H, W, 3 * W, y0, x0, h, w, self.ad.ptr(tables.buf), tables.nbytes, tables.tag,
+                                           int(bool(premultiply)), self._INGEST_FLOW[flow_dtype], self.ad.ptr(out_flow), self.ad.ptr(out_mask), Hd,
+                                           Wd, self.ad.stream(src_u16)))
+        return out_flow, out_mask
+
+    def cv_resize_u8(self, img, dst_hw, out=None):
+        """cv2.resize(img, (W', H')) of a uint8 (H, W, 3) device array, INTER_LINEAR (kitti.py:105-106, the test-set images)."""
+        shp = self.ad.shape(img)
+        if len(shp) != 3:
+            raise ValueError("cv_resize_u8: img has shape %s, expected (H, W, 3)" % (shp,))
+        return self.ingest_image(img, None, dst_hw, self.ingest_tables(shp[:2], dst_hw, like=img), out=out)
+
     def Upsample_backward(self, out_grad, factor, req="write", out=None):
         """Adjoint of Upsample(factor): (N,C,H*f,W*f) -> (N,C,H,W) (mfn_upsample_bwd)."""
         (go,) = self._in(out_grad)
@@ -1102,6 +1197,14 @@ class BatchRows:
         self.samples = list(samples)
 
 
+class IngestTables:
+    """Opaque device tables made by OpSet.ingest_tables: 32 bytes per destination column and row, and the tag that binds them to the
+    window size and the destination size."""
+
+    def __init__(self, buf, nbytes, tag, src_hw, dst_hw):
+        self.buf, self.nbytes, self.tag, self.src_hw, self.dst_hw = buf, int(nbytes), int(tag), tuple(src_hw), tuple(dst_hw)
+
+
 class TorchAdapter:
     """torch-ROCm tensors as device buffers; launches go to torch's current stream."""
 
@@ -1273,6 +1376,26 @@ def batch_gather_rows(*a, **k):
 
 def batch_gather(*a, **k):
     return default_ops().batch_gather(*a, **k)
+
+
+def ingest_tables(*a, **k):
+    return default_ops().ingest_tables(*a, **k)
+
+
+def ingest_minmax(*a, **k):
+    return default_ops().ingest_minmax(*a, **k)
+
+
+def ingest_image(*a, **k):
+    return default_ops().ingest_image(*a, **k)
+
+
+def ingest_flow_occ(*a, **k):
+    return default_ops().ingest_flow_occ(*a, **k)
+
+
+def cv_resize_u8(*a, **k):
+    return default_ops().cv_resize_u8(*a, **k)
 
 
 def Convolution(*a, **k):

@@ -56,6 +56,12 @@
 #define mfn_batch_gather_rows_bytes mfn_emu_batch_gather_rows_bytes
 #define mfn_batch_gather_build_rows mfn_emu_batch_gather_build_rows
 #define mfn_batch_gather mfn_emu_batch_gather
+#define mfn_ingest_tables_bytes mfn_emu_ingest_tables_bytes
+#define mfn_ingest_build_tables mfn_emu_ingest_build_tables
+#define mfn_ingest_minmax mfn_emu_ingest_minmax
+#define mfn_ingest_image mfn_emu_ingest_image
+#define mfn_ingest_flow_occ mfn_emu_ingest_flow_occ
+#define mfn_png_unfilter mfn_emu_png_unfilter
 #define mfn_conv2d_out_shape mfn_emu_conv2d_out_shape
 #define mfn_conv2d_workspace_bytes mfn_emu_conv2d_workspace_bytes
 #define mfn_conv2d_packed_weight_bytes mfn_emu_conv2d_packed_weight_bytes
@@ -378,6 +384,56 @@ static void others() {
                                                 (float *)((char *)lab.p + r.label_off), (unsigned char *)om.p, nullptr));
       for (Block *b : own) delete b;
     }
+  }
+  // raw arrays into stored samples (kernels/ingest.h): every source a heap block of exactly its size rounded up to 16 bytes (the read
+  // contract), every output and table of exactly its size; windows at odd byte offsets and against the array's last row and column,
+  // image sizes that end inside a 16-byte piece, pixel counts that end inside a quad, both flow types, the stretch
+  {
+    struct Row { const char *name; int H, W, y0, x0, h, w, Hd, Wd, bgr, stretch, pre, f16; };
+    const std::vector<Row> rows = {
+        {"ingest 13x21 of 17x29 -> 9x31", 17, 29, 3, 5, 13, 21, 9, 31, 1, 0, 0, 0},
+        {"ingest last rows / columns, stretch, fp16", 17, 29, 4, 8, 13, 21, 7, 27, 0, 1, 1, 1},
+        {"ingest 2x2 -> 5x3", 2, 2, 0, 0, 2, 2, 5, 3, 0, 1, 0, 1},
+        {"ingest equal sizes", 11, 19, 0, 0, 11, 19, 11, 19, 1, 0, 1, 0},
+        {"ingest 37x53 -> 70x150", 37, 53, 0, 0, 37, 53, 70, 150, 0, 1, 0, 0},
+    };
+    for (const Row &r : rows) {
+      auto bytes16 = [&](size_t n) {
+        Block *b = new Block((n + 15) & ~(size_t)15);
+        for (size_t i = 0; i < b->bytes; ++i) ((unsigned char *)b->p)[i] = (unsigned char)(rnd() * 127.f + 128.f);
+        return b;
+      };
+      const size_t px = (size_t)r.H * r.W, dpx = (size_t)r.Hd * r.Wd, need = mfn_ingest_tables_bytes(r.Hd, r.Wd);
+      Block *i1 = bytes16(3 * px), *i2 = bytes16(3 * px), *fo = bytes16(6 * px);
+      Block tab(need), mm(8), o1(3 * dpx), o2(3 * dpx), fl((r.f16 ? 4 : 8) * dpx), mk(dpx);
+      unsigned long long tag = 0;
+      int rc = mfn_ingest_build_tables(r.h, r.w, r.Hd, r.Wd, tab.p, need, &tag);
+      if (!rc && r.stretch) rc = mfn_ingest_minmax((const unsigned char *)i1->p, (const unsigned char *)i2->p, r.H, r.W, 3 * r.W, r.y0, r.x0, r.h, r.w, (unsigned *)mm.p, nullptr);
+      if (!rc) rc = mfn_ingest_image((const unsigned char *)i1->p, r.H, r.W, 3 * r.W, r.y0, r.x0, r.h, r.w, tab.p, need, tag, r.bgr, r.stretch ? (const unsigned *)mm.p : nullptr,
+                                     (unsigned char *)o1.p, r.Hd, r.Wd, nullptr);
+      if (!rc) rc = mfn_ingest_image((const unsigned char *)i2->p, r.H, r.W, 3 * r.W, r.y0, r.x0, r.h, r.w, tab.p, need, tag, r.bgr, r.stretch ? (const unsigned *)mm.p : nullptr,
+                                     (unsigned char *)o2.p, r.Hd, r.Wd, nullptr);
+      if (!rc) rc = mfn_ingest_flow_occ((const unsigned short *)fo->p, r.H, r.W, 3 * r.W, r.y0, r.x0, r.h, r.w, tab.p, need, tag, r.pre, r.f16, fl.p, (unsigned char *)mk.p,
+                                        r.Hd, r.Wd, nullptr);
+      report(r.name, rc);
+      delete i1; delete i2; delete fo;
+    }
+  }
+  // the PNG row filters (host code of the library): scanlines of every filter type, one and eight bytes per pixel, a row shorter than
+  // a pixel, the buffer a heap block of exactly rows * (1 + row_bytes) bytes; then a filter type that does not exist
+  {
+    struct Row { const char *name; long long rows, row_bytes; int bpp; };
+    for (const Row &r : {Row{"png_unfilter 11 x 37, 1 byte per pixel", 11, 37, 1}, Row{"png_unfilter 10 x 40, 8 bytes per pixel", 10, 40, 8},
+                         Row{"png_unfilter 7 x 3, 6 bytes per pixel", 7, 3, 6}, Row{"png_unfilter 1 x 1", 1, 1, 1}, Row{"png_unfilter no rows", 0, 5, 3}}) {
+      Block raw((size_t)(r.rows * (r.row_bytes + 1)));
+      for (size_t i = 0; i < raw.bytes; ++i) ((unsigned char *)raw.p)[i] = (unsigned char)(rnd() * 127.f + 128.f);
+      for (long long y = 0; y < r.rows; ++y) ((unsigned char *)raw.p)[y * (r.row_bytes + 1)] = (unsigned char)((y + 4) % 5);
+      report(r.name, mfn_png_unfilter((unsigned char *)raw.p, r.rows, r.row_bytes, r.bpp));
+    }
+    Block raw(2 * 6);
+    memset(raw.p, 0, raw.bytes);
+    ((unsigned char *)raw.p)[6] = 5;
+    report("png_unfilter refuses filter type 5", mfn_png_unfilter((unsigned char *)raw.p, 2, 5, 1) == MFN_E_PARAM ? 0 : -1);
   }
 }
 
