@@ -582,6 +582,10 @@ int mfn_get_arithmetic(const char *op, int *mode);
 /* Measurement only: when non-NULL, instrumented kernels write 4 x uint64 wall-clock stamps (100 MHz)
  * per workgroup into this device buffer (caller sizes it: 32 bytes x workgroups). */
 int mfn_debug_set_timeline(void *device_buffer);
+/* Measurement and tests only: the tiling the calling thread's last deformable-convolution launch on dc_mma_kernel was planned with --
+ * filter tiles per wave, pixel tiles per block, K slices, and whether the weight operand went from memory to registers (the AREG
+ * form, 1) or through LDS (0).  All zero before the first such launch.  Any pointer may be NULL. */
+int mfn_debug_last_dc_plan(int *mt, int *pt, int *kw, int *areg);
 int mfn_set_tuning(const char *key, int value);
 int mfn_get_tuning(const char *key, int *value);
 

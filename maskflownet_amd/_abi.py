@@ -36,6 +36,7 @@ SIGNATURES = {
     "deform_conv_shared_bwd_workspace_bytes": (C.c_size_t, [_i] * 12),
     "deform_conv_shared_bwd": (_i, [_f, _f, _f, C.c_float, C.c_float, _f, _f, _f, _f, _f] + [_i] * 16 + [C.c_void_p, C.c_size_t, _s]),
     "debug_set_timeline": (_i, [C.c_void_p]),
+    "debug_last_dc_plan": (_i, [_pi, _pi, _pi, _pi]),
     "correlation_bwd": (_i, [_f] * 5 + [_i] * 12 + [_s]),
     "warp_bwd": (_i, [_f] * 5 + [_i] * 7 + [_s]),
     "deform_conv_packed_weight_bytes": (C.c_size_t, [_i] * 15),

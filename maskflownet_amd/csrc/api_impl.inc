@@ -56,6 +56,7 @@ Tuning g_tuning;
 struct Arith { std::atomic<int> corr{-1}, deform{-1}, conv{-1}; };
 static Arith t_arith;
 void *g_timeline = nullptr;  // measurement only (mfn_debug_set_timeline)
+static thread_local int t_last_dc_plan[4] = {0, 0, 0, 0};  // mt, pt, kw, areg of this thread's last dc_mma launch (mfn_debug_last_dc_plan)
 // One reading of the process-wide settings.  Every exported entry point that plans takes it once (each atomic loaded once) and passes
 // it down, so that a call is planned from one set of values and every plan below is a function of its arguments.
 struct Settings { Tuning t; int corr, deform, conv; };
@@ -412,6 +413,7 @@ struct DcPlan {
   int mt, pt, nw, ksb, mgroups, ncp_pad, cps_per_slice;
   int mma;   // 0: exact fp32 (dc_lds_kernel); 2: the bf16 x 3 matrix-core kernel (dc_mma_kernel, deform_conv_mma.h)
   int kw, ring, groups, gps;   // mma == 2: K slices per pixel tile, window ring depth, 16-channel groups (per slice)
+  int areg;   // mma == 2: the weight operand from memory to registers (dc_mma_kernel's AREG form) instead of through LDS
   int tile_w, tiles_x, tiles_y, ntiles;
   size_t wt_bytes, partial_bytes, mg_words;
 };
@@ -419,6 +421,16 @@ struct DcPlan {
 #ifndef MFN_DCM_CONFIGS   // measurement builds instantiate fewer
 #define MFN_DCM_CONFIGS(X) X(1, 4, 1) X(2, 3, 4) X(2, 2, 2) X(3, 1, 6) X(1, 1, 8) X(1, 1, 4) X(1, 1, 2) X(1, 1, 1)
 #endif
+// ... and those it has the AREG form of (the tilings the plan gives the network's four levels)
+#ifndef MFN_DCM_AREG_CONFIGS
+#define MFN_DCM_AREG_CONFIGS(X) X(1, 4, 1) X(3, 1, 6) X(1, 1, 8)
+#endif
+static bool dcm_areg_config_ok(int mt, int pt, int kw) {
+#define X(a, b, c) if (mt == a && pt == b && kw == c) return true;
+  MFN_DCM_AREG_CONFIGS(X)
+#undef X
+  return false;
+}
 static bool dcm_config_ok(int mt, int pt, int kw) {
 #define X(a, b, c) if (mt == a && pt == b && kw == c) return true;
   MFN_DCM_CONFIGS(X)
@@ -469,6 +481,10 @@ static DcPlan dc_plan(const Settings &st, int Cin, int Cout, int N, int Ho, int 
     }
     if (!dcm_config_ok(cmt, cpt, ckw) || pl.groups % ckw != 0 || cmt > mtiles) { cmt = 1; cpt = 1; ckw = 1; }
     pl.mt = cmt; pl.pt = cpt; pl.kw = ckw; pl.nw = cpt * ckw; pl.ksb = 1;
+    // the weight operand from memory to registers wherever that form exists: it won at each of its tilings
+    // (profiles/dc_mma_a_operand.md).  dc.off bit 4 forces the LDS form (A/B runs and tests; the packed layout is the same); a
+    // tiling without the form keeps the LDS kernel whatever the bits say
+    pl.areg = dcm_areg_config_ok(cmt, cpt, ckw) && !(st.t.dc_off & 4);
     pl.mgroups = (mtiles + cmt - 1) / cmt;
     pl.gps = pl.groups / ckw;
     pl.mg_words = (size_t)(pl.groups * 9 + dcm_kc(cmt, ckw)) * (3 * cmt * 256);
@@ -671,8 +687,12 @@ static int dc_run(const Settings &st, DeformParams &p, const void *packed, size_
     p.dcm_groups = pl.groups;
     p.dcm_gps = pl.gps;
     p.xcd = pl.mgroups == 1 || cdiv(pl.ntiles, pl.pt) % 8 == 0;
-#define X(a, b, c) else if (pl.mt == a && pl.pt == b && pl.kw == c) rc = dc_mma_launch<a, b, c, 3>(p, s);
+    t_last_dc_plan[0] = pl.mt; t_last_dc_plan[1] = pl.pt; t_last_dc_plan[2] = pl.kw; t_last_dc_plan[3] = pl.areg;
+#define X(a, b, c) else if (pl.areg && pl.mt == a && pl.pt == b && pl.kw == c) rc = dc_mma_launch<a, b, c, 3, false, true>(p, s);
     if (false) {}
+    MFN_DCM_AREG_CONFIGS(X)
+#undef X
+#define X(a, b, c) else if (pl.mt == a && pl.pt == b && pl.kw == c) rc = dc_mma_launch<a, b, c, 3>(p, s);
     MFN_DCM_CONFIGS(X)
 #undef X
     if (rc == -1000) return fail(MFN_E_UNSUPPORTED, "%s: no matrix-core kernel for mt=%d pt=%d kw=%d", what, pl.mt, pl.pt, pl.kw);
@@ -2305,6 +2325,14 @@ int MFN_API(get_arithmetic)(const char *op, int *mode) {
   std::atomic<int> *slot = arith_slot(op);
   if (!slot || !mode) return fail(MFN_E_PARAM, "get_arithmetic: unknown operator '%s'", op ? op : "(null)");
   *mode = *slot;
+  return 0;
+}
+
+int MFN_API(debug_last_dc_plan)(int *mt, int *pt, int *kw, int *areg) {
+  if (mt) *mt = t_last_dc_plan[0];
+  if (pt) *pt = t_last_dc_plan[1];
+  if (kw) *kw = t_last_dc_plan[2];
+  if (areg) *areg = t_last_dc_plan[3];
   return 0;
 }
 

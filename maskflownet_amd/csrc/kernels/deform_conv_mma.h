@@ -107,7 +107,8 @@ constexpr int dcm_min_waves(int mt, int nw) {
 #define MFN_DCM_MINW(mt, nw) dcm_min_waves(mt, nw)
 #endif
 
-template <int MT, int PT, int KW, int RING> struct DcmGeom {
+// AREG: the weight operand goes from memory to registers (dc_mma_kernel's AREG form): the window rings start at word 0
+template <int MT, int PT, int KW, int RING, bool AREG = false> struct DcmGeom {
   static constexpr int NW = PT * KW, NTH = NW * 64;
   static constexpr int KC = dcm_kc(MT, KW);
   static constexpr int NSTAGE = dcm_nstage(MT, PT, KW, RING);
@@ -116,18 +117,21 @@ template <int MT, int PT, int KW, int RING> struct DcmGeom {
   static constexpr int NI = (WI_TOTAL + NW - 1) / NW;  // ... per wave at most; a wave whose last one would be past WI_TOTAL issues one fewer
   static constexpr int NI_MIN = WI_TOTAL / NW;         // ... at least: the waits count with this (a wave that issued one more waits for it too)
   static constexpr int STAGE_W = WI_TOTAL * 256;       // words per stage buffer
-  static constexpr int XW_OFF = NSTAGE * STAGE_W;
+  static constexpr int XW_OFF = AREG ? 0 : NSTAGE * STAGE_W;
   static constexpr int T8_OFF = XW_OFF + NW * RING * DCM_XW_F;      // tap 8 of a group's eight pairs: [wave][pair][lane]
-  static constexpr int DUMP_OFF = T8_OFF + NW * 512;
-  static constexpr int LDS_W = DUMP_OFF + 256;
-  static_assert(LDS_W * 4 <= 160 * 1024, "a block's LDS must fit the CU");
   // K-slice reduction: behind the loop nothing of the block's LDS is in use any more (stage buffers, window rings, tap-8 slots), and
   // every slice's MT partial tiles lie in it at once, from word 0: [pt][kw][mt][32 filter rows][RED_TS], the epilogue's transposed form
   // (a lane reads four adjacent pixels of a filter row with one 16-byte read; a D register's two half-waves write rows 4 apart,
   // 160 = 32 mod 64 words: disjoint banks)
   static constexpr int RED_TS = 40, RED_TILE = 32 * RED_TS;
   static constexpr int RED_W = KW > 1 ? PT * KW * MT * RED_TILE : 0;
-  static_assert(RED_W <= DUMP_OFF, "every slice's partial tiles fit the block's LDS at once");
+  // The block's LDS: stage buffers, window rings, tap-8 slots and 256 spare words.  DELIBERATELY the same in both forms: the AREG
+  // form has no stage buffers (XW_OFF = 0) and uses 65 / 90 / 33 KB of it at (1, 1, 8) / (3, 1, 6) / (1, 4, 1), the K-slice
+  // reduction included; the rest of the request is dead.  At those tilings the registers, not the LDS, set how many blocks a CU
+  // holds, so a smaller request buys nothing, and a call's launch geometry stays the recorded one (tests/data/dispatch_v1.json).
+  static constexpr int LDS_W = NSTAGE * STAGE_W + NW * RING * DCM_XW_F + NW * 512 + 256;
+  static_assert(LDS_W * 4 <= 160 * 1024, "a block's LDS must fit the CU");
+  static_assert(RED_W <= LDS_W - 256, "every slice's partial tiles fit the block's LDS at once");
   // ... summed and stored by ALL KW waves of the pixel tile: wave kw takes the slab [kw RED_SLAB, (kw + 1) RED_SLAB) of the 32 MT
   // filter rows, eight rows -- one per eight lanes -- at a time (a slab of four rows: half the wave)
   static constexpr int RED_ROWS = 32 * MT, RED_SLAB = RED_ROWS / KW, RED_PASSES = (RED_SLAB + 7) / 8;
@@ -141,21 +145,25 @@ template <int MT, int PT, int KW, int RING> struct DcmGeom {
 // issued after the youngest needed one.  1000 = nothing needed.
 // REQ: requests of the lanes outside the window (the tier that has them), issued behind the step's transfers by every step that
 // prepares a pair (all but step 7) -- they join the same in-order queue.
-template <int KC, int NSTAGE, int RING, int NI, int XW_NI, int REQ = 0> constexpr int dcm_wait_count(int s) {
+// AR: the AREG form (NI = 0: no weight transfers) -- every step requests, ahead of its window transfers, the AR register blocks of
+// the NEXT step's weight operand, and needs its own at its head; step 0's were waited for at the end of step 8 (dc_mma_kernel).
+template <int KC, int NSTAGE, int RING, int NI, int XW_NI, int REQ = 0, int AR = 0> constexpr int dcm_wait_count(int s) {
   int issued = 0, result = 1000;
-  int stampW[64] = {}, stampX[80] = {};
+  int stampW[64] = {}, stampX[80] = {}, stampA[48] = {};
   for (int u = 0; u < 45; ++u) {
     const int ss = u % 9, grp = u / 9;
     if (u == 36 + s) {
       int need = -1;
-      if (ss % KC == 0 && stampW[u / KC] > need) need = stampW[u / KC];
+      if (NI > 0 && ss % KC == 0 && stampW[u / KC] > need) need = stampW[u / KC];
+      if (AR > 0 && ss != 0 && stampA[u] > need) need = stampA[u];
       if (ss != 7) {
         const int np = ss == 8 ? 8 * (grp + 1) : 8 * grp + ss + 1;
         if (stampX[np] > need) need = stampX[np];
       }
       result = need < 0 ? 1000 : issued - need;
     }
-    if (ss % KC == 0) { issued += NI; stampW[u / KC + NSTAGE - 1] = issued; }
+    if (NI > 0 && ss % KC == 0) { issued += NI; stampW[u / KC + NSTAGE - 1] = issued; }
+    if (AR > 0) { issued += AR; stampA[u + 1] = issued; }
     if (ss < 8) { issued += XW_NI; stampX[8 * grp + ss + RING] = issued; }
     if (ss != 7) issued += REQ;
   }
@@ -163,11 +171,12 @@ template <int KC, int NSTAGE, int RING, int NI, int XW_NI, int REQ = 0> constexp
 }
 // ... and the count with which a preparing step (s != 7) waits for the requests it consumes -- those of the PREVIOUS preparing
 // step --, at the point behind its own transfers and requests: everything issued since
-template <int KC, int NSTAGE, int RING, int NI, int XW_NI, int REQ> constexpr int dcm_landed_count(int s) {
+template <int KC, int NSTAGE, int RING, int NI, int XW_NI, int REQ, int AR = 0> constexpr int dcm_landed_count(int s) {
   int issued = 0, last_req = 0, result = 0;
   for (int u = 0; u < 45; ++u) {
     const int ss = u % 9;
-    if (ss % KC == 0) issued += NI;
+    if (NI > 0 && ss % KC == 0) issued += NI;
+    issued += AR;
     if (ss < 8) issued += XW_NI;
     if (ss != 7) {
       issued += REQ;
@@ -229,10 +238,24 @@ struct DcmB { mfn_bf16x8 h, m, l; };
 // CONV: the plain 3x3 / stride 1 / pad 1 convolution on the same machinery (no offsets: the nine taps ARE the 3 x 3 pixels around the
 // output pixel, read straight from the window; Cin need not be a multiple of 16 -- the packed weights of the missing channels are
 // zero and their window transfers are suppressed; x and out may be channel slices of concat buffers).
-template <int MT, int PT, int KW, int RING, bool CONV = false>
+//
+// AREG: the weight operand of a K step goes from memory straight into registers instead of through stage buffers in LDS.
+// dcm_pack_weights_kernel writes the operand in the lanes' own layout -- lane (kb, m) owns the 16 bytes at word (kb 32 + m) 4 of each
+// 1 KB [term][ft] block --, so a wave asks for the 3 MT blocks of its OWN K slice's next step with one 16-byte request per block
+// (mfn_bload4_blocks_async: requests hipcc does not count, like those of the lanes outside the window) at the head of every step,
+// ahead of the window transfer, and waits for them with the window at the head of the next (dcm_wait_count's AR).  Two register
+// sets, A[0] / A[1], for the even / odd steps of a group; a group has nine steps, so the operand of the NEXT group's step 0 is
+// requested into A[1] by step 8, waited for at that step's end and copied to A[0] there (12 MT moves per group; nothing in
+// flight crosses the loop's back edge, see mfn_gload4_async on phi values).  No stage buffers (the loop uses the window rings and
+// the tap-8 slots, from word 0; DcmGeom::LDS_W on what the launch asks for), no issue_w, no block barrier in the loop at any PT: the waves of a K slice
+// share the blocks' cache lines, not a copy.  Same products in the same order: every output bit is that of the LDS form.
+// The per-tap tier reads its weights from the same packed array with plain loads.  CONV keeps the LDS form.
+template <int MT, int PT, int KW, int RING, bool CONV = false, bool AREG = false>
 __global__ __launch_bounds__(PT * KW * 64, MFN_DCM_MINW(MT, PT * KW)) void dc_mma_kernel(DeformParams p) {
-  using G = DcmGeom<MT, PT, KW, RING>;
-  constexpr int NW = G::NW, KC = G::KC, NI = G::NI, NIW = G::NI_MIN;
+  static_assert(!(CONV && AREG), "the plain-convolution form keeps the LDS path");
+  using G = DcmGeom<MT, PT, KW, RING, AREG>;
+  constexpr int NW = G::NW, KC = G::KC, NI = G::NI, NIW = AREG ? 0 : G::NI_MIN;
+  constexpr int AR = AREG ? 3 * MT : 0;   // register blocks requested per step
   constexpr int NACC = MT == 1 ? 2 : 1;   // MT = 1: two accumulators take the products alternately (no dependent MFMA pair)
   // One pixel tile per block: every wave is a K slice of its own and nobody shares its weights -- each wave then transfers exactly
   // its own slice's blocks into its part of the stage buffers and the K loop needs NO block barrier (a wave's own program order
@@ -272,20 +295,30 @@ __global__ __launch_bounds__(PT * KW * 64, MFN_DCM_MINW(MT, PT * KW)) void dc_mm
     float *buf = lds + (ch % G::NSTAGE) * G::STAGE_W;
     // a chunk past the slice's last step (the unconditional prefetch) is requested out of range: zero fill, no memory access
     const unsigned soff = ch * KC < gps * 9 ? (unsigned)((size_t)ch * KC * G::STEP_W * 4) : 0x7FFFFF00u;
-    if (MFN_DCM_ABLATE & 32) return;
+    if (AREG || (MFN_DCM_ABLATE & 32)) return;
     MFN_UNROLL
     for (int i = 0; i < NI; ++i) {
       const int ii = PRIVATE_W ? wave * (KC * 3 * MT) + i : i * NW + wave;
       if (ii < G::WI_TOTAL) mfn_dma16_so(wrsrc, buf + ii * 256, voffW[i], soff);   // wave-uniform
     }
   };
+  // AREG: the operand's two register sets, block b = term MT + ft as in the packed step, and the request of step st of this
+  // wave's K slice into one of them (a step past the slice is requested out of range, the rule of issue_w: zeros, no access)
+  f32x4 A[2][3 * MT];
+  const unsigned voffA = (unsigned)(((size_t)(wave % KW) * gps * 9) * G::STEP_W * 4) + (unsigned)lane * 16u;
+  auto request_a = [&](int st, auto set_c) {
+    mfn_bload4_blocks_async(A[decltype(set_c)::value], wrsrc, voffA, (unsigned)((size_t)st * G::STEP_W * 4), st < gps * 9);
+  };
 
   // The prologue's weight chunks (0 .. NSTAGE - 2) depend on nothing below: they are requested HERE, ahead of the offset loads, so
   // that their way from memory lies under the offsets' round trip, the geometry and the window box instead of behind them.
   // (Transfers complete in issue order: hipcc's own wait for the offset loads, which it counts, covers these older transfers
-  // too -- the offsets are then back when chunk 0 is, not before.)
-  MFN_UNROLL
-  for (int ch = 0; ch < G::NSTAGE - 1; ++ch) issue_w(ch);
+  // too -- the offsets are then back when chunk 0 is, not before.)  AREG: the first step's operand instead.
+  if constexpr (AREG) request_a(0, std::integral_constant<int, 0>{});
+  else {
+    MFN_UNROLL
+    for (int ch = 0; ch < G::NSTAGE - 1; ++ch) issue_w(ch);
+  }
 
   // ---- the wave's pixel tile: 4 rows x 8 columns of one image ---------------------------------------------------------
   int n, ty, tx;
@@ -618,6 +651,15 @@ __global__ __launch_bounds__(PT * KW * 64, MFN_DCM_MINW(MT, PT * KW)) void dc_mm
       am[ft] = mfn_read_bf16x8(a + (1 * MT + ft) * 256);
     }
   };
+  auto a_from = [&](auto set_c) {   // AREG: this step's blocks are in a register set already
+    constexpr int SET = decltype(set_c)::value;
+    MFN_UNROLL
+    for (int ft = 0; ft < MT; ++ft) {
+      ah[ft] = mfn_bf16x8_of(A[SET][0 * MT + ft]);
+      am[ft] = mfn_bf16x8_of(A[SET][1 * MT + ft]);
+      al[ft] = mfn_bf16x8_of(A[SET][2 * MT + ft]);
+    }
+  };
   auto mma_issue = [&](const DcmB &b) {
     if (MFN_DCM_ABLATE & 1) {
       MFN_UNROLL
@@ -676,6 +718,7 @@ __global__ __launch_bounds__(PT * KW * 64, MFN_DCM_MINW(MT, PT * KW)) void dc_mm
     // transfers follow window k than the count of the step that gathers it allows to be outstanding.  (Windows 1 .. DEPTH - 1 were
     // issued back to back with window 0.)
     MFN_WAIT_VM(0);
+    if constexpr (AREG) mfn_landed_blocks<0>(A[0]);   // (the prologue's request: step 0's operand)
     float x8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, c8 = 0.f;
     if (fast) {
       if (decltype(out_c)::value) lanes_request(0, std::integral_constant<int, 1>{});
@@ -713,13 +756,18 @@ __global__ __launch_bounds__(PT * KW * 64, MFN_DCM_MINW(MT, PT * KW)) void dc_mm
       mfn_static_for<9>([&](auto s_c) {
         constexpr int S = decltype(s_c)::value;
         constexpr bool OUT = decltype(out_c)::value;
-        constexpr int NWAIT = dcm_wait_count<KC, G::NSTAGE, WN::DEPTH, NIW, WN::NI, OUT ? 16 : 0>(S);
-        if (NWAIT < 1000) MFN_WAIT_VM(NWAIT < 63 ? NWAIT : 63);
+        constexpr int NWAIT = dcm_wait_count<KC, G::NSTAGE, WN::DEPTH, NIW, WN::NI, OUT ? 16 : 0, AR>(S);
+        // (AREG: the same wait with this step's operand registers, A[S & 1], named -- step 0's landed at the end of step 8)
+        if constexpr (AREG && S != 0) mfn_landed_blocks<(NWAIT < 63 ? NWAIT : 63)>(A[S & 1]);
+        else if (NWAIT < 1000) MFN_WAIT_VM(NWAIT < 63 ? NWAIT : 63);
         const int ch = g * CPG + S / KC;
         constexpr int kk = S % KC;
         const int kn = S == 8 ? (g + 1) * 8 : g * 8 + S + 1;   // the pair in preparation under this step's products
         constexpr int E = S == 8 ? 7 : S;   // the group's E-th preparation (steps 0..6 and 8)
-        if (kk == 0) {   // this chunk's weights landed for every wave; everybody is done with the stage that is refilled now
+        if constexpr (AREG) {   // the next step's operand -> the other set
+          if (S == 0 && g == 0) MFN_STAMP(p.timeline, 1);
+          request_a(g * 9 + S + 1, std::integral_constant<int, (S + 1) & 1>{});
+        } else if (kk == 0) {   // this chunk's weights landed for every wave; everybody is done with the stage that is refilled now
           MFN_WAIT_LGKM0();
           if (!PRIVATE_W && !(MFN_DCM_ABLATE & 128)) MFN_RAW_BARRIER();
           if (S == 0 && g == 0) MFN_STAMP(p.timeline, 1);
@@ -730,12 +778,13 @@ __global__ __launch_bounds__(PT * KW * 64, MFN_DCM_MINW(MT, PT * KW)) void dc_mm
         if (OUT && S != 7) lanes_request(S == 8 ? g * 8 + 9 : g * 8 + S + 2, std::integral_constant<int, (E + 1) & 1>{});
         const float *a = lds + (ch % G::NSTAGE) * G::STAGE_W + (size_t)(kw * KC + kk) * G::STEP_W + (kb * 32 + j) * 4;
         float x8[8];
-        a_read(a);
+        if constexpr (AREG) a_from(std::integral_constant<int, S & 1>{});
+        else a_read(a);
         if (S != 7) cols_gather(kn, win_c);
         mma_issue(B);
         if (OUT && S != 7)
           lanes_landed(std::integral_constant<int, E & 1>{},
-                       std::integral_constant<int, dcm_landed_count<KC, G::NSTAGE, WN::DEPTH, NIW, WN::NI, 16>(S)>{});
+                       std::integral_constant<int, dcm_landed_count<KC, G::NSTAGE, WN::DEPTH, NIW, WN::NI, 16, AR>(S)>{});
         if (S == 7) {   // the left-over step's operand: tap 8 of the eight pairs
           MFN_UNROLL
           for (int e = 0; e < 8; ++e) x8[e] = xt8[e * 64];
@@ -752,6 +801,11 @@ __global__ __launch_bounds__(PT * KW * 64, MFN_DCM_MINW(MT, PT * KW)) void dc_mm
           else mfn_split3x8_scalar(x8, B.h, B.m, B.l);
         }
 #endif
+        if constexpr (AREG && S == 8) {   // the next group's first operand: behind it only this step's requests of the lanes outside
+          mfn_landed_blocks<(OUT ? 16 : 0)>(A[1]);
+          MFN_UNROLL
+          for (int b = 0; b < 3 * MT; ++b) A[0][b] = A[1][b];
+        }
         MFN_SCHED_BARRIER();
       });
     }
@@ -771,14 +825,18 @@ __global__ __launch_bounds__(PT * KW * 64, MFN_DCM_MINW(MT, PT * KW)) void dc_mm
         if (NWAIT < 1000 && MASK != 0 && ((MASK >> s) & 1u)) MFN_WAIT_VM(NWAIT < 63 ? NWAIT : 63);
       });
       const int ch = t / KC, kk = t - ch * KC;
-      if (kk == 0) {
+      if (AREG) {   // no stage buffers, no barrier: the other waves of the block have none either
+        if (t == 0) MFN_STAMP(p.timeline, 1);
+      } else if (kk == 0) {
         MFN_WAIT_LGKM0();
         if (!PRIVATE_W) MFN_RAW_BARRIER();
         if (t == 0) MFN_STAMP(p.timeline, 1);
         issue_w(ch + G::NSTAGE - 1);
       }
       if (s < 8) issue_x(kl + WN::DEPTH, WN{});   // (zero-filled: keeps the transfer sequence, hence the counts, those of the window tiers)
-      const float *a = lds + (ch % G::NSTAGE) * G::STAGE_W + (size_t)(kw * KC + kk) * G::STEP_W + (kb * 32 + j) * 4;
+      // AREG: step t's blocks of this wave's K slice where dcm_pack_weights_kernel put them, read with plain loads
+      const float *a = AREG ? p.wt + (size_t)mg * mg_words + ((size_t)kw * gps * 9 + t) * G::STEP_W + (kb * 32 + j) * 4
+                            : lds + (ch % G::NSTAGE) * G::STAGE_W + (size_t)(kw * KC + kk) * G::STEP_W + (kb * 32 + j) * 4;
       if (s < 8) pertap_pair(kl, a, xt8 + (kl & 7) * 64);
       else { a_read(a); mma_issue(B); }
       if (s == 7) {
@@ -933,12 +991,12 @@ __global__ __launch_bounds__(PT * KW * 64, MFN_DCM_MINW(MT, PT * KW)) void dc_mm
   MFN_STAMP(p.timeline, 3);
 }
 
-template <int MT, int PT, int KW, int RING, bool CONV = false>
+template <int MT, int PT, int KW, int RING, bool CONV = false, bool AREG = false>
 inline int dc_mma_launch(const DeformParams &p, hipStream_t stream, const char *name = "dc_mma") {
-  using G = DcmGeom<MT, PT, KW, RING>;
+  using G = DcmGeom<MT, PT, KW, RING, AREG>;
   const int bx = cdiv(p.ntiles, PT);
   if (bx <= 0) return 0;
-  return launch(name, dc_mma_kernel<MT, PT, KW, RING, CONV>, dim3(bx, 1, p.mgroups), dim3(G::NTH), (size_t)G::LDS_W * sizeof(float), stream, p);
+  return launch(name, dc_mma_kernel<MT, PT, KW, RING, CONV, AREG>, dim3(bx, 1, p.mgroups), dim3(G::NTH), (size_t)G::LDS_W * sizeof(float), stream, p);
 }
 // the plain-convolution form: 3x3 / stride 1 / pad 1 / dilation 1, one group, 16-byte rows; any channel count
 inline bool dcm_conv_shape_ok(int N, size_t x_nstride, int H, int W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int groups) {

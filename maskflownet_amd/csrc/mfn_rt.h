@@ -175,6 +175,17 @@ static inline void mfn_bload1x4_async(float &d0, float &d1, float &d2, float &d3
     else *d[k] = 0.f;
   }
 }
+// NB blocks of 1 KB, sixteen bytes per lane of each (block b at byte offset 1024 b), through a raw buffer descriptor with a
+// wave-uniform soffset: out of range (or !live) reads zeros.  Synchronous here.
+template <int NB> static inline void mfn_bload4_blocks_async(f32x4_emu (&d)[NB], mfn_rsrc_t r, unsigned voff, unsigned soff, bool live) {
+  for (int b = 0; b < NB; ++b) {
+    const unsigned long long off = (unsigned long long)voff + soff + 1024u * b;
+    if (live && off + 16 <= r.nrec) memcpy(&d[b], r.base + off, 16);
+    else memset(&d[b], 0, 16);
+  }
+}
+template <int N, int NB> static inline void mfn_landed_blocks(f32x4_emu (&)[NB]) { hipemu::wave().bar.arrive_and_wait(); }   // a wait: as MFN_WAIT_VM
+static inline mfn_bf16x8 mfn_bf16x8_of(const f32x4_emu &q) { mfn_bf16x8 v; memcpy(&v, &q, 16); return v; }
 #define MFN_LANDED4(a, b, c, d, n) ((void)0)
 #define MFN_REGFENCE4(a, b, c, d) ((void)0)
 #define MFN_REGFENCE9(v) ((void)0)
@@ -578,6 +589,46 @@ __device__ __forceinline__ void mfn_bload1x4_async(float &d0, float &d1, float &
 // fence on the registers behind the join -- a LANDED4 per branch makes the destinations phi values, and hipcc resolved
 // those with register copies placed BEFORE the waits (copies of data that has not landed)
 #define MFN_REGFENCE4(a, b, c, d) asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : : "memory")
+// The sixteen-byte counterpart of mfn_bload1x4_async, all lanes: NB (3, 6 or 9) blocks of 1 KB, sixteen bytes per lane of each --
+// block b at byte offset 1024 b behind voff + soff, as the instruction's immediate (up to 3072) on one of up to three soffsets 4 KB
+// apart -- in ONE statement, so that every scalar it reads is formed before its s_nop.  !live: every block is requested out of
+// range (zeros, no memory access).  Unknown to hipcc: the registers hold data only behind mfn_landed_blocks on them.
+template <int NB>
+__device__ __forceinline__ void mfn_bload4_blocks_async(f32x4 (&d)[NB], mfn_rsrc_t rsrc, unsigned voff, unsigned soff, bool live) {
+  static_assert(NB == 3 || NB == 6 || NB == 9, "one, two or three filter tiles of three terms");
+  const unsigned s0 = __builtin_amdgcn_readfirstlane(live ? soff : 0x7FFFFF00u);
+  const unsigned s1 = __builtin_amdgcn_readfirstlane(live ? soff + 4096u : 0x7FFFFF00u);
+  const unsigned s2 = __builtin_amdgcn_readfirstlane(live ? soff + 8192u : 0x7FFFFF00u);
+  if constexpr (NB == 3) {
+    asm volatile("s_nop 4\n\tbuffer_load_dwordx4 %0, %3, %4, %5 offen\n\tbuffer_load_dwordx4 %1, %3, %4, %5 offen offset:1024\n\t"
+                 "buffer_load_dwordx4 %2, %3, %4, %5 offen offset:2048"
+                 : "=&v"(d[0]), "=&v"(d[1]), "=&v"(d[2]) : "v"(voff), "s"(rsrc), "s"(s0) : "memory");
+  } else if constexpr (NB == 6) {
+    asm volatile("s_nop 4\n\tbuffer_load_dwordx4 %0, %6, %7, %8 offen\n\tbuffer_load_dwordx4 %1, %6, %7, %8 offen offset:1024\n\t"
+                 "buffer_load_dwordx4 %2, %6, %7, %8 offen offset:2048\n\tbuffer_load_dwordx4 %3, %6, %7, %8 offen offset:3072\n\t"
+                 "buffer_load_dwordx4 %4, %6, %7, %9 offen\n\tbuffer_load_dwordx4 %5, %6, %7, %9 offen offset:1024"
+                 : "=&v"(d[0]), "=&v"(d[1]), "=&v"(d[2]), "=&v"(d[3]), "=&v"(d[4]), "=&v"(d[5]) : "v"(voff), "s"(rsrc), "s"(s0), "s"(s1) : "memory");
+  } else {
+    asm volatile("s_nop 4\n\tbuffer_load_dwordx4 %0, %9, %10, %11 offen\n\tbuffer_load_dwordx4 %1, %9, %10, %11 offen offset:1024\n\t"
+                 "buffer_load_dwordx4 %2, %9, %10, %11 offen offset:2048\n\tbuffer_load_dwordx4 %3, %9, %10, %11 offen offset:3072\n\t"
+                 "buffer_load_dwordx4 %4, %9, %10, %12 offen\n\tbuffer_load_dwordx4 %5, %9, %10, %12 offen offset:1024\n\t"
+                 "buffer_load_dwordx4 %6, %9, %10, %12 offen offset:2048\n\tbuffer_load_dwordx4 %7, %9, %10, %12 offen offset:3072\n\t"
+                 "buffer_load_dwordx4 %8, %9, %10, %13 offen"
+                 : "=&v"(d[0]), "=&v"(d[1]), "=&v"(d[2]), "=&v"(d[3]), "=&v"(d[4]), "=&v"(d[5]), "=&v"(d[6]), "=&v"(d[7]), "=&v"(d[8])
+                 : "v"(voff), "s"(rsrc), "s"(s0), "s"(s1), "s"(s2) : "memory");
+  }
+}
+// ... and their MFN_LANDED4: the wait (at most N younger requests outstanding) with the registers named read-write
+template <int N, int NB> __device__ __forceinline__ void mfn_landed_blocks(f32x4 (&d)[NB]) {
+  static_assert(NB == 3 || NB == 6 || NB == 9, "as mfn_bload4_blocks_async");
+  if constexpr (NB == 3) asm volatile("s_waitcnt vmcnt(%3)" : "+v"(d[0]), "+v"(d[1]), "+v"(d[2]) : "n"(N) : "memory");
+  else if constexpr (NB == 6)
+    asm volatile("s_waitcnt vmcnt(%6)" : "+v"(d[0]), "+v"(d[1]), "+v"(d[2]), "+v"(d[3]), "+v"(d[4]), "+v"(d[5]) : "n"(N) : "memory");
+  else
+    asm volatile("s_waitcnt vmcnt(%9)" : "+v"(d[0]), "+v"(d[1]), "+v"(d[2]), "+v"(d[3]), "+v"(d[4]), "+v"(d[5]), "+v"(d[6]), "+v"(d[7]), "+v"(d[8])
+                 : "n"(N) : "memory");
+}
+__device__ __forceinline__ mfn_bf16x8 mfn_bf16x8_of(const f32x4 &q) { return __builtin_bit_cast(mfn_bf16x8, q); }
 // nine values are COMPUTED here (hipcc otherwise sinks the arithmetic that forms them next to its use, one pipeline step
 // later, and keeps the registers it reads alive across the request that is about to overwrite them)
 #define MFN_REGFENCE9(v) asm volatile("" : "+v"((v)[0]), "+v"((v)[1]), "+v"((v)[2]), "+v"((v)[3]), "+v"((v)[4]), "+v"((v)[5]), "+v"((v)[6]), "+v"((v)[7]), "+v"((v)[8]))

@@ -24,7 +24,9 @@
 //   dc.ksb        K split across blocks (partial sums + reduce kernel); 0 = heuristic
 //   dc.nw         waves per block: 0 auto, 4, 8 (8 only with pt = 1)
 //   dc.off        bits that switch tiers of the shared-offset forward path off: 1 = the LDS source-window staging (every tile on
-//                 the global-gather tier), 2 = the shared-offset 4x4-neighbourhood gather altogether (per-tap path)
+//                 the global-gather tier), 2 = the shared-offset 4x4-neighbourhood gather altogether (per-tap path), 4 = the
+//                 memory-to-register feed of dc_mma_kernel's weight operand (the AREG form: every tiling then stages the operand in
+//                 LDS; without the bit the plan takes the AREG form at every tiling that has it)
 //   path.generic  bits that force the generic one-thread-per-output kernels: 1 = correlation, 2 = deformable convolution
 //                 (forward and backward), 4 = convolution
 //   bwd.off       bits that switch backward kernels off: 1 = the lane = pixel shared-offset input / offset gradient (tap by tap
