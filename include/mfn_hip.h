@@ -305,6 +305,39 @@ int mfn_flow_metrics(const float *flow, const float *label, const float *mask, f
                      void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Prediction on uint8 frame sequences and the colour picture of a flow -- replace the arithmetic of the
+ * reference's /root/reference/predict_new_data.py around `pipe.predict(prev_frames, new_frames)` (:152-158) for frames that are on
+ * the device as bytes.  kernels/frames.h spells out every expression.
+ * frames: (F,H,W,3) uint8, HWC.  A batch of N pairs is two first indices: pair n is (frames[a0+n], frames[b0+n]) -- a video passes
+ * b0 = a0 + 1, two stacked lists b0 = a0 + N.  No alignment is asked of `frames`: wider-than-byte loads are taken only where the
+ * address allows them.
+ * Errors before any launch: a NULL tensor (MFN_E_NULL); N, a0 or b0 < 0, a0 + N > F, b0 + N > F, H, W, Hout or Wout < 1
+ * (MFN_E_SHAPE, the message names the argument); a missing or short workspace (MFN_E_WORKSPACE); a float pointer that is not 4-byte
+ * aligned (MFN_E_ALIGN).  N == 0 succeeds and touches nothing. */
+/* rgb_mean of pipeline.py:86 for the images bytes / 255 of pipeline.py:208, EXACT: per (n, c) the 2 H W bytes are summed as integers
+ * (fixed order through the workspace, no atomics) and mean[n,c] = (float)((double)sum / (255.0 * 2 H W)): order-independent,
+ * bit-identical to np.float32(np.float64(sum) / np.float64(255 * 2 * H * W)).  Not the bits of mfn_pair_mean on byte / 255 floats,
+ * which sums rounded quotients in fp32.  mean: (N,3). */
+size_t mfn_pair_mean_u8_workspace_bytes(int N, int H, int W);
+int mfn_pair_mean_u8(const unsigned char *frames, int F, int H, int W, int a0, int b0, int N, float *mean, void *workspace,
+                     size_t workspace_bytes, void *stream);
+/* pipeline.py:208 (`/ 255`, HWC -> CHW), :120 and :129-130 in one launch: mfn_preprocess_pair reading byte taps, each
+ * (float)byte / 255.f.  out: (2N,3,Hout,Wout), image 1 in rows [0,N), image 2 in rows [N,2N).  Bit-identical to
+ * mfn_preprocess_pair on the floats byte / 255.f with the same mean.  mean_or_null: (N,3), NULL subtracts nothing.  Hout == H and
+ * Wout == W unpacks the bytes into float CHW (- mean). */
+int mfn_preprocess_pair_u8(const unsigned char *frames, int F, int H, int W, int a0, int b0, int N, const float *mean_or_null,
+                           float *out, int Hout, int Wout, void *stream);
+/* [flow_vis-ext, unpinned] flow_vis.flow_to_color(flow_uv, convert_to_bgr=bgr) of predict_new_data.py:155,:158 (no clip_flow),
+ * restated from memory in kernels/frames.h: the Middlebury colour wheel (55 colours), hue from the direction, saturation from
+ * |flow| / (rad_max + 1e-5), in fp32.  flow: (N,2,H,W) in network order (channel 0 = dy); rgb: (N,H,W,3) uint8, channels reversed
+ * with bgr != 0.  rad_max >= 0: the scale of every image (one scale for a video); rad_max < 0: each image's own maximum of
+ * sqrtf(u*u + v*v) over its finite values, found through the workspace in a fixed order; NaN: MFN_E_PARAM.  A pixel whose flow is
+ * not finite is written (0,0,0).  The workspace is asked for in both forms. */
+size_t mfn_flow_color_workspace_bytes(int N, int H, int W);
+int mfn_flow_color(const float *flow, unsigned char *rgb, int N, int H, int W, float rad_max, int bgr, void *workspace,
+                   size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Augmentation of the training batch -- replace the device side of the two augmenters that
  * /root/reference/network/pipeline.py:100-101 applies before every step: GeometryAugmentation
  * (/root/reference/augmentation.py:229-339) and ColorAugmentation (:168-227).  The per-sample scalars are drawn on the host

@@ -111,6 +111,12 @@ PRODUCT_ONLY = {
     "bilinear_resize_fwd": (_i, [_f, _f, _f] + [_i] * 7 + [_s]),
     "flow_metrics_workspace_bytes": (C.c_size_t, [_i] * 3),
     "flow_metrics": (_i, [_f, _f, _f, _f] + [_i] * 3 + [C.c_void_p, C.c_size_t, _s]),
+    # prediction on uint8 frame sequences, the colour picture of a flow (kernels/frames.h): product only, like the entries above
+    "pair_mean_u8_workspace_bytes": (C.c_size_t, [_i] * 3),
+    "pair_mean_u8": (_i, [C.c_void_p] + [_i] * 6 + [_f, C.c_void_p, C.c_size_t, _s]),
+    "preprocess_pair_u8": (_i, [C.c_void_p] + [_i] * 6 + [_f, _f, _i, _i, _s]),
+    "flow_color_workspace_bytes": (C.c_size_t, [_i] * 3),
+    "flow_color": (_i, [_f, C.c_void_p, _i, _i, _i, C.c_float, _i, C.c_void_p, C.c_size_t, _s]),
 }
 
 

@@ -19,6 +19,7 @@
 #include "kernels/warp.h"
 #include "kernels/upsample.h"
 #include "kernels/predict.h"
+#include "kernels/frames.h"
 #include "kernels/augment.h"
 #include "kernels/loss.h"
 #include "kernels/optimizer.h"
@@ -932,6 +933,82 @@ int MFN_API(flow_metrics)(const float *flow, const float *label, const float *ma
   if (!aligned(workspace, 4)) return fail(MFN_E_ALIGN, "flow_metrics: workspace must be 4-byte aligned");
   FlowMetricsParams p{flow, label, mask, (float *)workspace, sums, plane, N, slices};
   return hipfail(flow_metrics_launch(p, (hipStream_t)stream), "flow_metrics");
+}
+
+// ---- prediction on uint8 frame sequences, the colour picture of a flow (kernels/frames.h) -----------------------------------
+// what every frames entry accepts: positive sizes, both index ranges inside [0, F), a frame inside what one launch indexes
+static int frames_dims(const char *what, int F, int H, int W, int a0, int b0, int N) {
+  if (N < 0) return fail(MFN_E_SHAPE, "%s: N=%d is negative", what, N);
+  if (F < 0) return fail(MFN_E_SHAPE, "%s: F=%d is negative", what, F);
+  if (H < 1 || W < 1) return fail(MFN_E_SHAPE, "%s: H=%d W=%d must be >= 1", what, H, W);
+  if (a0 < 0) return fail(MFN_E_SHAPE, "%s: a0=%d is negative", what, a0);
+  if (b0 < 0) return fail(MFN_E_SHAPE, "%s: b0=%d is negative", what, b0);
+  if ((long long)a0 + N > F) return fail(MFN_E_SHAPE, "%s: a0 + N = %lld leaves the F=%d frames", what, (long long)a0 + N, F);
+  if ((long long)b0 + N > F) return fail(MFN_E_SHAPE, "%s: b0 + N = %lld leaves the F=%d frames", what, (long long)b0 + N, F);
+  if ((size_t)H * W * 3 >= ((size_t)1 << 31)) return fail(MFN_E_UNSUPPORTED, "%s: frame too large", what);
+  return 0;
+}
+
+size_t MFN_API(pair_mean_u8_workspace_bytes)(int N, int H, int W) {
+  if (N <= 0 || H <= 0 || W <= 0) return 0;
+  return (size_t)N * pred_slices((size_t)2 * H * W) * 3 * sizeof(unsigned);
+}
+
+int MFN_API(pair_mean_u8)(const unsigned char *frames, int F, int H, int W, int a0, int b0, int N, float *mean, void *workspace,
+                          size_t workspace_bytes, void *stream) {
+  if (N != 0 && (!frames || !mean)) return fail(MFN_E_NULL, "pair_mean_u8: NULL tensor pointer");
+  if (int rc = frames_dims("pair_mean_u8", F, H, W, a0, b0, N)) return rc;
+  if (N == 0) return 0;
+  const size_t plane = (size_t)H * W;
+  if (int rc = reduce_dims("pair_mean_u8", (size_t)N, 2 * plane)) return rc;
+  const int slices = pred_slices(2 * plane);
+  const size_t need = (size_t)N * slices * 3 * sizeof(unsigned);
+  if (!workspace || workspace_bytes < need)
+    return fail(MFN_E_WORKSPACE, "pair_mean_u8: workspace of %zu bytes needed, %zu given", need, workspace ? workspace_bytes : (size_t)0);
+  if (!aligned(workspace, 4) || !aligned(mean, 4)) return fail(MFN_E_ALIGN, "pair_mean_u8: mean and workspace must be 4-byte aligned");
+  PairMeanU8Params p{frames, (unsigned *)workspace, mean, plane, 255.0 * (double)(2 * plane), a0, b0, N, slices};
+  return hipfail(pair_mean_u8_launch(p, (hipStream_t)stream), "pair_mean_u8");
+}
+
+int MFN_API(preprocess_pair_u8)(const unsigned char *frames, int F, int H, int W, int a0, int b0, int N, const float *mean_or_null,
+                                float *out, int Hout, int Wout, void *stream) {
+  if (N != 0 && (!frames || !out)) return fail(MFN_E_NULL, "preprocess_pair_u8: NULL tensor pointer");
+  if (int rc = frames_dims("preprocess_pair_u8", F, H, W, a0, b0, N)) return rc;
+  if (Hout < 1 || Wout < 1) return fail(MFN_E_SHAPE, "preprocess_pair_u8: Hout=%d Wout=%d must be >= 1", Hout, Wout);
+  if (int rc = resize_dims("preprocess_pair_u8", N, 3, H, W, Hout, Wout)) return rc;
+  if (N == 0) return 0;
+  if (!aligned(out, 4) || !aligned(mean_or_null, 4)) return fail(MFN_E_ALIGN, "preprocess_pair_u8: mean and out must be 4-byte aligned");
+  FramesPreParams p{};
+  p.frames = frames; p.mean = mean_or_null; p.out = out;
+  p.a0 = a0; p.b0 = b0; p.N = N;
+  p.H = H; p.W = W; p.Hout = Hout; p.Wout = Wout;
+  p.ry = Hout > 1 ? (float)(H - 1) / (float)(Hout - 1) : 0.f;
+  p.rx = Wout > 1 ? (float)(W - 1) / (float)(Wout - 1) : 0.f;
+  p.st_policy = store_policy_for(settings_now(), (size_t)6 * N * Hout * Wout * 4, 2, -1);
+  return hipfail(frames_pre_launch(p, (hipStream_t)stream), "preprocess_pair_u8");
+}
+
+size_t MFN_API(flow_color_workspace_bytes)(int N, int H, int W) {
+  if (N <= 0 || H <= 0 || W <= 0) return 0;
+  return (size_t)N * (pred_slices((size_t)H * W) + 1) * sizeof(float);
+}
+
+int MFN_API(flow_color)(const float *flow, unsigned char *rgb, int N, int H, int W, float rad_max, int bgr, void *workspace,
+                        size_t workspace_bytes, void *stream) {
+  if (N != 0 && (!flow || !rgb)) return fail(MFN_E_NULL, "flow_color: NULL tensor pointer");
+  if (N < 0 || H < 1 || W < 1) return fail(MFN_E_SHAPE, "flow_color: N=%d H=%d W=%d", N, H, W);
+  if (rad_max != rad_max) return fail(MFN_E_PARAM, "flow_color: rad_max is NaN");
+  if (N == 0) return 0;
+  const size_t plane = (size_t)H * W;
+  if ((size_t)N * plane * 3 >= ((size_t)1 << 32)) return fail(MFN_E_UNSUPPORTED, "flow_color: tensor too large");
+  if (int rc = reduce_dims("flow_color", (size_t)N, plane)) return rc;
+  const int slices = pred_slices(plane);
+  const size_t need = (size_t)N * (slices + 1) * sizeof(float);
+  if (!workspace || workspace_bytes < need)
+    return fail(MFN_E_WORKSPACE, "flow_color: workspace of %zu bytes needed, %zu given", need, workspace ? workspace_bytes : (size_t)0);
+  if (!aligned(workspace, 4) || !aligned(flow, 4)) return fail(MFN_E_ALIGN, "flow_color: flow and workspace must be 4-byte aligned");
+  FlowColorParams p{flow, rgb, (float *)workspace, (float *)workspace + (size_t)N * slices, rad_max, N, H, W, slices, bgr ? 1 : 0};
+  return hipfail(flow_color_launch(p, (hipStream_t)stream), "flow_color");
 }
 
 // ---- augmentation of the training batch: geometry, colour (kernels/augment.h) ---------------------------------------------

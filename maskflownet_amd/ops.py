@@ -912,6 +912,58 @@ class OpSet:
                                            Wd, self.ad.stream(src_u16)))
         return out_flow, out_mask
 
+    # ---- prediction on uint8 frame sequences, the colour picture of a flow (predict_new_data.py:152-158) -----------------------------
+    def _frames(self, frames, a0, b0, n, what):
+        self._raw(frames, what + ": frames", ("uint8",))
+        shp = self.ad.shape(frames)
+        if len(shp) != 4 or shp[3] != 3:
+            raise ValueError("%s: frames has shape %s, expected (F, H, W, 3)" % (what, shp))
+        return tuple(int(v) for v in shp[:3]) + (int(a0), int(b0), int(n))
+
+    def pair_mean_u8(self, frames, a0, b0, n, out=None):
+        """rgb_mean of PipelineFlownet.centralize (pipeline.py:86) for the n pairs (frames[a0+k], frames[b0+k]) of a uint8 (F,H,W,3)
+        device array read as bytes / 255: -> (n,3), exact (integer sums; mfn_pair_mean_u8), not the bits of pair_mean on floats."""
+        what = "pair_mean_u8"
+        F, H, W, a0, b0, n = self._frames(frames, a0, b0, n, what)
+        out = self._out(out, frames, (n, 3), what)
+        ws = self._workspace(frames, self.ns.pair_mean_u8_workspace_bytes(n, H, W))
+        self.check(self.ns.pair_mean_u8(self.ad.ptr(frames), F, H, W, a0, b0, n, self.ad.ptr(out), self.ad.ptr(ws), self.ad.nbytes(ws),
+                                        self.ad.stream(frames)))
+        return out
+
+    def preprocess_pair_u8(self, frames, a0, b0, n, height, width, mean=None, out=None):
+        """preprocess_pair reading the bytes of a uint8 (F,H,W,3) device array, every tap (float)byte / 255.f (pipeline.py:208,
+        :120-130): -> (2n,3,height,width), frames[a0+k] in row k and frames[b0+k] in row n + k; the bits of preprocess_pair on those
+        floats.  mean (n,3): subtracted from every tap; None subtracts nothing.  height == H and width == W unpacks."""
+        what = "preprocess_pair_u8"
+        F, H, W, a0, b0, n = self._frames(frames, a0, b0, n, what)
+        m = None
+        if mean is not None:
+            (m,) = self._in(mean)
+            if self.ad.shape(m) != (n, 3):
+                raise ValueError("%s: mean must have shape %s, got %s" % (what, (n, 3), self.ad.shape(m)))
+        out = self._out(out, frames, (2 * n, 3, int(height), int(width)), what)
+        self.check(self.ns.preprocess_pair_u8(self.ad.ptr(frames), F, H, W, a0, b0, n, self.ad.ptr(m) if m is not None else None,
+                                              self.ad.ptr(out), int(height), int(width), self.ad.stream(frames)))
+        return out
+
+    def flow_color(self, flow, rad_max=None, bgr=False, out=None):
+        """flow_vis.flow_to_color(flow, convert_to_bgr=bgr) of predict_new_data.py:155,:158 ([flow_vis-ext, unpinned]; mfn_flow_color):
+        flow (N,2,H,W) in network order (channel 0 = dy) -> uint8 (N,H,W,3).  rad_max: the radius that saturates the colours, one for
+        all images; None takes each image's own largest finite radius."""
+        what = "flow_color"
+        (f,) = self._in(flow)
+        if self.ad.ndim(f) != 4 or self.ad.shape(f)[1] != 2:
+            raise ValueError("%s: flow must be (N,2,H,W), got %s" % (what, self.ad.shape(f)))
+        if rad_max is not None and not float(rad_max) >= 0.0:
+            raise ValueError("%s: rad_max must be >= 0 or None, got %r" % (what, rad_max))
+        N, _, H, W = self.ad.shape(f)
+        out = self._raw_out(f, (N, H, W, 3), "uint8", out, what + ": out")
+        ws = self._workspace(f, self.ns.flow_color_workspace_bytes(N, H, W))
+        self.check(self.ns.flow_color(self.ad.ptr(f), self.ad.ptr(out), N, H, W, -1.0 if rad_max is None else float(rad_max), int(bool(bgr)),
+                                      self.ad.ptr(ws), self.ad.nbytes(ws), self.ad.stream(f)))
+        return out
+
     def cv_resize_u8(self, img, dst_hw, out=None):
         """cv2.resize(img, (W', H')) of a uint8 (H, W, 3) device array, INTER_LINEAR (kitti.py:105-106, the test-set images)."""
         shp = self.ad.shape(img)
@@ -1396,6 +1448,18 @@ def ingest_flow_occ(*a, **k):
 
 def cv_resize_u8(*a, **k):
     return default_ops().cv_resize_u8(*a, **k)
+
+
+def pair_mean_u8(*a, **k):
+    return default_ops().pair_mean_u8(*a, **k)
+
+
+def preprocess_pair_u8(*a, **k):
+    return default_ops().preprocess_pair_u8(*a, **k)
+
+
+def flow_color(*a, **k):
+    return default_ops().flow_color(*a, **k)
 
 
 def Convolution(*a, **k):

@@ -12,6 +12,11 @@ and `Predictor` is that sequence: four HIP kernels of csrc/kernels/predict.h (jo
 images straight into the network's input batch, resize back, metric sums) plus Upsample and warp, enqueued on the
 network's own stream around one replay of its hipGraph, one synchronisation per batch.  The resize arithmetic is MXNet
 1.5's (align_corners, fp32 positions; include/mfn_hip.h), not torch's.
+
+Frame sequences (the reference's predict_new_data.py: an image pair or the consecutive frames of a video, :100-118, :152-158)
+stay bytes until they are on the device: `do_batch_u8` / `predict_frames` upload every uint8 HWC frame once, take the joint mean
+and the network's input batch straight from the bytes (csrc/kernels/frames.h) and can colour the flows there
+(flow_vis.flow_to_color, restated and unpinned); `python -m maskflownet_amd.predict` is the command line on top of them.
 """
 import numpy as np
 
@@ -58,6 +63,7 @@ class Predictor:
         self.resized = (self.H64, self.W64) != (self.H, self.W)
         self.net = (network.MaskFlownet if full else network.MaskFlownetS)(params, self.N, self.H64, self.W64, device)
         self.dev, self.stream = self.net.dev, self.net.stream
+        self.frames_uploaded = 0            # frames that predict_frames sent to the device: one per frame of the sequence
         N, H, W = self.N, self.H, self.W
         with torch.cuda.stream(self.stream):
             e = lambda *shape: torch.empty(*shape, device=self.dev)
@@ -117,6 +123,125 @@ class Predictor:
         self.stream.synchronize()
         return {"flow": flow[:n], "occ_mask": occ[:n], "warped": b["warped"][:n], "epe": epe, "fl": fl}
 
+    # ---- uint8 frame sequences on the device (predict_new_data.py:100-118, :152-158) ------------------------------------------------
+    def _rows_u8(self, frames, f0, n, height, width, mean, dst):
+        """dst[k] <- frames[f0 + min(k, n - 1)] through preprocess_pair_u8 with mean[min(k, n - 1)], for every row of dst: the first n
+        rows and the last of them repeated.  A launch of m pairs writes 2m adjacent rows with ONE set of m means, so a launch here is
+        (x, x, m): rows [s, s + m) and the same again in [s + m, s + 2m), which a later launch overwrites or, for the last frame, is
+        the repeat asked for.  About log2(n) + (rows - n) / 2 launches; no frame is copied."""
+        ops, rows, s = self.ops, int(dst.shape[0]), 0
+        while s < rows:
+            if s >= n - 1:                       # the last frame and its repeats: identical rows, two per launch
+                r, x, m = min(s, rows - 2), f0 + n - 1, 1
+            else:                                # the second copy stays inside dst and in front of the last frame's row
+                r, x, m = s, f0 + s, min(n - 1 - s, (rows - s) // 2)
+            ops.preprocess_pair_u8(frames, x, x, m, height, width, mean=None if mean is None else mean[x - f0:x - f0 + m],
+                                   out=dst[r:r + 2 * m])
+            s = r + 2 if s >= n - 1 else s + m
+
+    def _fill_u8(self, frames, a0, b0, n, height, width, mean, dst):
+        """dst (2N,3,height,width) <- the n pairs (frames[a0+k], frames[b0+k]), image 1 in rows [0,N), image 2 in rows [N,2N); a short
+        batch repeats its last pair (index arithmetic, one launch for a full batch)."""
+        if n == self.N:
+            self.ops.preprocess_pair_u8(frames, a0, b0, n, height, width, mean=mean, out=dst)
+        else:
+            self._rows_u8(frames, a0, n, height, width, mean, dst[:self.N])
+            self._rows_u8(frames, b0, n, height, width, mean, dst[self.N:])
+
+    def _enqueue_u8(self, frames, a0, b0, n, label, mask, warped):
+        t, ops, b, net, N = self.torch, self.ops, self.b, self.net, self.N
+        a0, b0, n = int(a0), int(b0), int(n)
+        if not isinstance(frames, t.Tensor) or frames.dtype != t.uint8 or frames.dim() != 4 or tuple(frames.shape[1:]) != (self.H, self.W, 3):
+            raise ValueError("do_batch_u8: frames must be a uint8 (F,%d,%d,3) device tensor, got %s %s"
+                             % (self.H, self.W, getattr(frames, "dtype", type(frames)), tuple(getattr(frames, "shape", ()))))
+        if not 1 <= n <= N:
+            raise ValueError("do_batch_u8: %d pairs for a Predictor of batch %d" % (n, N))
+        with t.cuda.stream(self.stream):
+            ops.pair_mean_u8(frames, a0, b0, n, out=b["mean"][:n])                         # pipeline.py:86 on bytes / 255 (:208)
+            self._fill_u8(frames, a0, b0, n, self.H64, self.W64, b["mean"], net.b["im"])   # :120-130
+            net.replay()
+            flow64 = net.b["gflow_full" if self.full else "flow_full"]
+            ops.Upsample(net.b["occlusion"], 4, out=b["occ64"])
+            if self.resized:
+                flow = ops.bilinear_resize(flow64, self.H, self.W, flow_rescale=True, out=b["flow"])
+                occ = ops.bilinear_resize(b["occ64"], self.H, self.W, out=b["occ"])
+            else:
+                flow, occ = flow64, b["occ64"]
+            if warped:
+                if "im12" not in b:            # image 1 and image 2 as floats, one (2N,3,H,W) buffer: what one unpack launch writes
+                    b["im12"] = t.empty(2 * N, 3, self.H, self.W, device=self.dev)
+                self._fill_u8(frames, a0, b0, n, self.H, self.W, None, b["im12"])
+                ops.warp(b["im12"][N:], flow, clip_grid=True, out=b["warped"])
+            epe = fl = None
+            if label is not None:
+                self._load(b["label"], label, n, "label")
+                if mask is None:
+                    b["mask"].fill_(1.0)
+                else:
+                    self._load(b["mask"], mask, n, "mask")
+                ops.flow_metric_sums(flow, b["label"], b["mask"], out=b["sums"])
+                epe, fl = (b["sums"][:n, 0] / b["sums"][:n, 1]), (b["sums"][:n, 2] / b["sums"][:n, 1])
+        return flow, {"flow": flow[:n], "occ_mask": occ[:n], "warped": b["warped"][:n] if warped else None, "epe": epe, "fl": fl}
+
+    def do_batch_u8(self, frames, a0, b0, n, label=None, mask=None, warped=True):
+        """do_batch on bytes that are already on the device.  frames: (F,H,W,3) uint8 device tensor, HWC; the n <= batch pairs are
+        (frames[a0+k], frames[b0+k]) -- a video passes b0 = a0 + 1, two stacked lists b0 = a0 + n.  The joint mean is the exact one of
+        ops.pair_mean_u8 (one fp32 rounding away from do_batch's on the same images); everything after it is do_batch's sequence.
+        warped=False skips the unpacking of the frames into floats and the warp, and returns None for it.  -> do_batch's dict."""
+        out = self._enqueue_u8(frames, a0, b0, n, label, mask, warped)[1]
+        self.stream.synchronize()
+        return out
+
+    def predict_frames(self, frames, color=False, rad_max=None, bgr=False, warped=False):
+        """Generator over an iterable of HWC uint8 frames (predict_video_flow, predict_new_data.py:100-118): per consecutive pair
+        (flow (H,W,2) in (u,v) order, occ_mask (H,W,1), warped (H,W,3) or None), with color=True followed by the colour picture
+        (H,W,3) uint8 of the flow (flow_vis.flow_to_color, :155,:158; rad_max, bgr as ops.flow_color).  Every frame crosses to the device
+        once, as bytes (self.frames_uploaded counts them): a batch's last frame stays there as the first of the next.  One
+        synchronisation per batch."""
+        t, N = self.torch, self.N
+        if "frames" not in self.b:
+            with t.cuda.stream(self.stream):
+                self.b["frames"] = t.empty(N + 1, self.H, self.W, 3, dtype=t.uint8, device=self.dev)
+                self.b["rgb"] = t.empty(N, self.H, self.W, 3, dtype=t.uint8, device=self.dev)
+        fb, have, new = self.b["frames"], 0, []     # have: 1 once slot 0 holds the frame that opens the next batch
+
+        def run(new):
+            nonlocal have
+            host = np.stack([self._frame_u8(f) for f in new])
+            n = have + len(new) - 1                 # pairs: slots (k, k + 1)
+            with t.cuda.stream(self.stream):
+                fb[have:have + len(new)].copy_(t.from_numpy(host), non_blocking=True)
+                self.frames_uploaded += len(new)
+                flow_all, out = self._enqueue_u8(fb, 0, 1, n, None, None, warped)
+                rgb = self.ops.flow_color(flow_all, rad_max=rad_max, bgr=bgr, out=self.b["rgb"]) if color else None
+            self.stream.synchronize()
+            flow = np.flip(out["flow"].cpu().numpy().transpose(0, 2, 3, 1), axis=-1)
+            occ = out["occ_mask"].cpu().numpy().transpose(0, 2, 3, 1)
+            wrp = out["warped"].cpu().numpy().transpose(0, 2, 3, 1) if warped else None
+            pic = rgb[:n].cpu().numpy() if color else None
+            with t.cuda.stream(self.stream):
+                fb[0].copy_(fb[n])                  # the carry-over, device to device; ordered behind the kernels that read slot 0
+            have = 1
+            for k in range(n):
+                res = (np.ascontiguousarray(flow[k]), np.ascontiguousarray(occ[k]), np.ascontiguousarray(wrp[k]) if warped else None)
+                yield res + (pic[k].copy(),) if color else res
+
+        for f in frames:
+            new.append(f)
+            if have + len(new) == N + 1:
+                yield from run(new)
+                new = []
+        if have + len(new) >= 2:
+            yield from run(new)
+        elif not have:
+            raise ValueError("predict_frames: at least two frames are needed, got %d" % len(new))
+
+    def _frame_u8(self, img):
+        a = np.asarray(img)
+        if a.dtype != np.uint8 or a.shape != (self.H, self.W, 3):
+            raise ValueError("predict_frames: a uint8 (%d,%d,3) frame is expected, got %s %s" % (self.H, self.W, a.dtype, a.shape))
+        return a
+
     def _batches(self, *lists):
         size = len(lists[0])
         if any(len(l) != size for l in lists):
@@ -148,3 +273,63 @@ class Predictor:
             out = self.do_batch(np.stack([_chw01(a) for a in im1]), np.stack([_chw01(a) for a in im2]), lab, m)
             vals.append((out["epe"] if return_type == "epe" else out["fl"]).cpu().numpy())
         return float(np.mean(np.concatenate(vals)))
+
+
+# ---- command line: the reference's predict_new_data.py for an image pair or a directory of frames ---------------------------------
+def _read_bgr(path):
+    """A .png or .ppm file as cv2.imread hands it to the reference (predict_new_data.py:152-153): (H,W,3) uint8 in BGR order."""
+    from . import io
+    a = io.read_ppm(path) if path.lower().endswith(".ppm") else io.read_png(path)
+    if a.dtype != np.uint8:
+        raise ValueError("%s: an 8-bit image is expected, got %s" % (path, a.dtype))
+    if a.ndim == 2:
+        a = a[..., None]
+    if a.shape[2] in (1, 2):                # gray (+ alpha): cv2.imread's three equal channels
+        a = np.repeat(a[..., :1], 3, axis=2)
+    return np.ascontiguousarray(a[..., 2::-1])
+
+
+def main(argv=None):
+    """python -m maskflownet_amd.predict OUT --params FILE [--full] [--resize H,W] [--batch B] [--rad_max R]
+    (--image_1 A --image_2 B | --frames DIR): the colour picture of the flow of an image pair as the PNG file OUT, or of every
+    consecutive pair of the sorted .png / .ppm files of DIR as OUT/%06d.png.  Video containers are not read: there is no decoder."""
+    import argparse
+    import os
+    from . import io
+    ap = argparse.ArgumentParser(prog="python -m maskflownet_amd.predict", description=main.__doc__)
+    ap.add_argument("out", help="destination: a PNG file (image pair) or a directory (frames)")
+    ap.add_argument("--params", required=True, help="checkpoint in MXNet's NDArray-list format")
+    ap.add_argument("--full", action="store_true", help="MaskFlownet (default: MaskFlownet-S)")
+    ap.add_argument("--resize", default="", help="H,W the network runs at (default: the next multiples of 64)")
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--rad_max", type=float, default=None, help="flow radius that saturates the colours (default: each picture's largest)")
+    ap.add_argument("--image_1")
+    ap.add_argument("--image_2")
+    ap.add_argument("--frames", help="directory of .png / .ppm frames, taken in sorted order")
+    args = ap.parse_args(argv)
+    if (args.frames is None) == (args.image_1 is None) or (args.image_1 is None) != (args.image_2 is None):
+        ap.error("give --image_1 and --image_2, or --frames")
+    resize = [int(s) for s in args.resize.split(",")] if args.resize else None
+    if args.frames is not None:
+        names = sorted(f for f in os.listdir(args.frames) if f.lower().endswith((".png", ".ppm")))
+        paths = [os.path.join(args.frames, f) for f in names]
+    else:
+        paths = [args.image_1, args.image_2]
+    if len(paths) < 2:
+        ap.error("at least two frames are needed, found %d" % len(paths))
+    first = _read_bgr(paths[0])
+    batch = max(1, min(args.batch, len(paths) - 1))
+    p = Predictor(network.from_reference_keys(io.load_params(args.params)), batch, first.shape[0], first.shape[1], full=args.full, resize=resize)
+    frames = (first if k == 0 else _read_bgr(q) for k, q in enumerate(paths))
+    pictures = (out[3] for out in p.predict_frames(frames, color=True, rad_max=args.rad_max, bgr=False))
+    if args.frames is None:
+        io.write_png(args.out, next(pictures))
+    else:
+        os.makedirs(args.out, exist_ok=True)
+        for k, pic in enumerate(pictures):
+            io.write_png(os.path.join(args.out, "%06d.png" % k), pic)
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())
