@@ -73,7 +73,8 @@ def _check(what, arith, got, want64, ref32, M, base=None):
 
 
 # ---- the cases ---------------------------------------------------------------------------------------------------------------
-def case_corr_bwd(env, arith, shape, md, gkind, req="write", seed=0):
+def case_corr_bwd(env, arith, shape, md, gkind, req="write", seed=0, kernels=("corr_bwd_lds",), reqs=None):
+    """reqs: (req of g1, req of g2), 'write' or 'null' each, in place of `req` for both: a gradient that is not asked for comes back None."""
     N, C, H, W = shape
     D = 2 * md + 1
     rng = np.random.default_rng(700 + seed)
@@ -96,11 +97,16 @@ def case_corr_bwd(env, arith, shape, md, gkind, req="write", seed=0):
         if req == "add":
             g1, g2 = env.ops.Correlation_backward(env.dev(go), env.dev(f1), env.dev(f2), 1, md, 1, 1, md, True, req1="add", req2="add",
                                                   g1=env.dev(base[0].copy()), g2=env.dev(base[1].copy()))
+        elif reqs is not None:
+            g1, g2 = env.ops.Correlation_backward(env.dev(go), env.dev(f1), env.dev(f2), 1, md, 1, 1, md, True, req1=reqs[0], req2=reqs[1])
         else:
             g1, g2 = env.ops.Correlation_backward(env.dev(go), env.dev(f1), env.dev(f2), 1, md, 1, 1, md, True)
-    what = "corr bwd %s md=%d %s %s" % (shape, md, gkind, req)
-    L.expect(["corr_bwd_lds"], what=what)
-    for g, w64, r32, m, b, nm in zip((g1, g2), want64, ref32, M, base, ("g1", "g2")):
+    what = "corr bwd %s md=%d %s %s" % (shape, md, gkind, req if reqs is None else "/".join(reqs))
+    L.expect(list(kernels), what=what)
+    for g, w64, r32, m, b, nm, rq in zip((g1, g2), want64, ref32, M, base, ("g1", "g2"), reqs or (req, req)):
+        if rq == "null":
+            assert g is None, "%s %s: req null, but an output came back" % (what, nm)
+            continue
         _check("%s %s" % (what, nm), arith, env.host(g), w64, r32, m, base=b)
 
 
@@ -137,8 +143,9 @@ def case_deform_bwd(env, arith, N, Cin, Cout, H, W, kind, gkind, input_kernel="d
         _check("%s %s" % (what, nm), arith, env.host(g), w64, r32, m)
 
 
-def case_deform_flow_bwd(env, arith, N, C, H, W, gkind, scale=20.0, stride=8.0, seed=0):
-    """mfn_deform_conv_shared_bwd in flow mode: d/dflow = scale / stride * sum over the taps, against the summed bound."""
+def case_deform_flow_bwd(env, arith, N, C, H, W, gkind, scale=20.0, stride=8.0, seed=0, kernels=None, req=("write",) * 4):
+    """mfn_deform_conv_shared_bwd in flow mode: d/dflow = scale / stride * sum over the taps, against the summed bound.  kernels: the
+    call's launches where they are not the bench levels'; req: (gx, gflow, gw, gbias), 'write' or 'null' each."""
     rng, x, w, go = _dc_inputs(N, C, C, H, W, gkind, 50 + seed)
     # flows on a 2^-10 grid below 2^7: flow * 20 / 8 (and flow * 2.5) are exact, the offsets on the exact_positions grid
     fl = exact_positions(pc.flow_field(rng, N, H, W) * np.float32(stride / scale), 2.0 ** -10)
@@ -155,10 +162,16 @@ def case_deform_flow_bwd(env, arith, N, C, H, W, gkind, scale=20.0, stride=8.0, 
     ref32, want64, M = _cached(("flow", (N, C, H, W), gkind, seed), make)
     env.set_arith("deform", arith)
     with env.launches() as L:
-        got = env.ops.deformable_convolution_shared_backward(env.dev(go), env.dev(x), env.dev(fl), scale, stride, env.dev(w))
-    what = "deform flow bwd %s %s" % ((N, C, H, W), gkind)
-    L.expect(["dc_bwd_input_pix", "dc_bwd_weight_pc"], absent=["offsets_from_flow"], what=what)
-    for g, w64, r32, m, nm in zip(got, want64, ref32, M, ("gx", "gflow", "gw", "gbias")):
+        got = env.ops.deformable_convolution_shared_backward(env.dev(go), env.dev(x), env.dev(fl), scale, stride, env.dev(w), req=tuple(req))
+    what = "deform flow bwd %s %s%s" % ((N, C, H, W), gkind, "" if tuple(req) == ("write",) * 4 else " req=" + "".join(r[0] for r in req))
+    if kernels is None:
+        L.expect(["dc_bwd_input_pix", "dc_bwd_weight_pc"], absent=["offsets_from_flow"], what=what)
+    else:
+        L.expect(list(kernels), what=what)
+    for g, w64, r32, m, nm, rq in zip(got, want64, ref32, M, ("gx", "gflow", "gw", "gbias"), req):
+        if rq == "null":
+            assert g is None, "%s %s: req null, but an output came back" % (what, nm)
+            continue
         _check("%s %s" % (what, nm), arith, env.host(g), w64, r32, m)
 
 

@@ -360,3 +360,16 @@ def test_unlisted_corr_variants_leave_the_choice_to_the_library(dry_ops):
         tune = {"corr_variant": variant}
         got = _flat(_entries(dry_ops, [tune]))
         assert {k.replace(_name(tune), "default"): v for k, v in got.items()} == default, variant
+
+
+def test_tall_image_leaves_the_gram_kernel_only_beyond_its_block_range(dry_ops):
+    """(1, 32, 400000, 8) under corr.variant = 48: 8-row items make 50 000 blocks, inside the range of the Gram-band kernel's magic
+    divisions, and it runs; corr.rows = 6 makes 66 667, beyond it (corr_gram_range_ok), and the plan falls back to the tiled kernel --
+    which is also its own choice at this shape.  tests/test_gpu_parity.py runs the three calls."""
+    got = {}
+    for name, tune in (("rows8", dict(corr_variant=48)), ("rows6", dict(corr_variant=48, corr_rows=6)), ("plan", {})):
+        emu_ops.set_tuning(**dict(DEFAULT_TUNING, **tune))
+        assert _corr_call(dry_ops.ns, (1, 32, 400000, 8), 4)[0] == 0
+        got[name] = [(r[0], r[1]) for r in emu_ops.dry_launches()]
+    assert got["rows8"] == [("corr_gram_v48", 50000)]
+    assert got["rows6"] == got["plan"] == [("corr_tiled_v6", 12500)]

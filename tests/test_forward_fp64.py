@@ -135,6 +135,11 @@ def _structural(what, got, Mz, b):
     return int(z.sum())
 
 
+def _names(kernel):
+    """One kernel name, or the list of a call's launches."""
+    return [kernel] if isinstance(kernel, str) else list(kernel)
+
+
 def case_deform(env, arith, N, C, H, W, okind, kind, kernel, bias="usual", tuning=None, packed=False, seed=0):
     """The drop-in DeformableConvolution at offsets of `okind` on the exact_positions grid."""
     rng = np.random.default_rng(1800 + seed)
@@ -145,13 +150,13 @@ def case_deform(env, arith, N, C, H, W, okind, kind, kernel, bias="usual", tunin
     r32, r64, Mz = _cached(("deform", (N, C, H, W), okind, kind, bias, seed), lambda: _dc_oracles(x, off, w, b))
     M = Mz + (np.abs(b.astype(np.float64))[None, :, None, None] if b is not None else 0.0)
     env.set_arith("deform", arith)
-    what = "deform %s %s %s bias=%s %s%s" % ((N, C, H, W), okind, kind, bias if b is not None else "no", kernel, " packed" if packed else "")
+    what = "deform %s %s %s bias=%s %s%s" % ((N, C, H, W), okind, kind, bias if b is not None else "no", "+".join(_names(kernel)), " packed" if packed else "")
     kw = dict(kernel=(3, 3), pad=(1, 1), num_filter=C, no_bias=b is None)
     xd, od, wd, bd = env.dev(x), env.dev(off), env.dev(w), env.dev(b) if b is not None else None
     with _tuned(env, tuning):
         with env.launches() as L:
             got = env.host(env.ops.DeformableConvolution(xd, od, wd, bd, **kw))
-        L.expect([kernel], what=what)
+        L.expect(_names(kernel), what=what)
         if packed:   # weights packed once give the per-call path's bits
             pk = env.ops.pack_deform_weights(wd, (N, C, H, W), kernel=(3, 3), pad=(1, 1))
             np.testing.assert_array_equal(env.host(env.ops.DeformableConvolution(xd, od, wd, bd, packed=pk, **kw)), got)
@@ -185,18 +190,18 @@ def case_deform_flow(env, arith, N, C, H, W, kind, kernel, bias="usual", scale=2
 
     r32, r64, Mz, Mb, tr, m32, m64, Mm = _cached(("flow", (N, C, H, W), kind, bias, seed), make)
     env.set_arith("deform", arith)
-    what = "deform %s flow %s bias=%s %s" % ((N, C, H, W), kind, bias if b is not None else "no", kernel)
+    what = "deform %s flow %s bias=%s %s" % ((N, C, H, W), kind, bias if b is not None else "no", "+".join(_names(kernel)))
     xd, fd, wd, bd = env.dev(x), env.dev(fl), env.dev(w), env.dev(b) if b is not None else None
     with env.launches() as L:
         got = env.host(env.ops.deformable_convolution_shared(xd, fd, scale, stride, wd, bd))
-    L.expect([kernel], absent=["offsets_from_flow", "offsets_from_flow_v4"], what=what + " shared")
+    L.expect(_names(kernel), absent=["offsets_from_flow", "offsets_from_flow_v4"], what=what + " shared")
     dropin = env.host(env.ops.DeformableConvolution(xd, env.dev(off), wd, bd, kernel=(3, 3), pad=(1, 1), num_filter=C, no_bias=b is None))
     np.testing.assert_array_equal(got, dropin, err_msg=what + ": the fused-offset call differs from the drop-in call")
     _structural(what, got, Mz, b)
     _check(what + " shared", arith, got, r64, r32, Mb)
     with env.launches() as L:
         got = env.host(env.ops.deformable_matching(xd, fd, scale, stride, wd, bd, env.dev(mask), env.dev(tr), leaky=True))
-    L.expect([kernel], what=what + " matching")
+    L.expect(_names(kernel), what=what + " matching")
     _check(what + " matching", arith, got, m64, m32, Mm)
 
 

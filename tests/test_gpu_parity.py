@@ -182,16 +182,26 @@ def test_correlation_numeric_range_edge_cases(ops, oracle, dev):
 
 
 def test_correlation_of_a_very_tall_image_leaves_the_gram_kernel(ops, oracle, dev, T):
-    """400 000 rows x 8 columns x 32 channels: beyond the Gram-band kernel's block-index range (its magic divisions need block id x
-    divisor < 2^32).  The plan asks (corr_gram_range_ok) and another kernel runs -- round 6 found the launch answering with an error
-    instead.  Checked on a crop against the oracle (the operator is local: rows y depend on rows y - 4 .. y + 4)."""
+    """400 000 rows x 8 columns x 32 channels, around the end of the Gram-band kernel's block-index range (its magic divisions need block
+    id x divisor < 2^32).  With 8-row items (corr.variant = 48 at this shape) the 50 000 blocks are inside it and the Gram kernel runs;
+    with 6-row items (corr.rows = 6) the 66 667 blocks are beyond it: the plan asks (corr_gram_range_ok) and another kernel runs -- round
+    6 found the launch answering with an error instead.  The plan's own choice at this shape is the tiled kernel.  Which kernel ran is
+    read from the launch record; tests/test_dispatch_table.py pins the same plans on the CPU.  Checked on crops against the oracle (the
+    operator is local: rows y depend on rows y - 4 .. y + 4)."""
     from maskflownet_amd import _lib
+    from tests.fp64_env import Launches
     g = T.Generator(device="cuda").manual_seed(5)
     f1 = T.randn(1, 32, 400000, 8, device="cuda", generator=g)
     f2 = T.randn(1, 32, 400000, 8, device="cuda", generator=g)
-    for variant in (48, -1):
-        _lib.set_tuning(corr_variant=variant)
-        out = ops.Correlation(f1, f2, 1, 4, 1, 1, 4)
+    for variant, rows, gram in ((48, 0, True), (48, 6, False), (-1, 0, False)):
+        _lib.set_tuning(corr_variant=variant, corr_rows=rows)
+        with Launches(emu=False) as L:
+            out = ops.Correlation(f1, f2, 1, 4, 1, 1, 4)
+        what = "tall image, corr.variant=%d corr.rows=%d" % (variant, rows)
+        if gram:
+            L.expect(["corr_gram_v48"], absent=["corr_tiled_v6"], what=what)
+        else:
+            L.expect(["corr_tiled_v6"], absent=["corr_gram"], what=what)
         for y0 in (0, 199990, 399980):
             a, b = max(y0 - 4, 0), min(y0 + 24, 400000)
             want = oracle.correlation(f1[:, :, a:b].cpu().numpy(), f2[:, :, a:b].cpu().numpy(), max_displacement=4, pad_size=4)
@@ -1023,11 +1033,12 @@ def test_hot_path_prepacked_equals_stateless(T):
         assert T.equal(u, v)
 
 
-@pytest.mark.parametrize("cfg", [(1, 128, 192), (3, 192, 256), (2, 256, 448), (5, 64, 64)])
+@pytest.mark.parametrize("cfg", [(1, 128, 192), (3, 192, 256), (2, 256, 448), (5, 64, 64), (1, 320, 448)])
 @pytest.mark.parametrize("mode", ["dropin", "fused"])
 def test_hot_path_pass_other_batch_and_image_sizes(T, cfg, mode):
     """The launch plans (tile kernels, channel groups, band / direct kernels, pixel tiles per block, 8-wave blocks) are
-    functions of the shape: the whole pass at other batch sizes and resolutions, every output against the oracle."""
+    functions of the shape: the whole pass at other batch sizes and resolutions, every output against the oracle.  (1, 320, 448) is
+    the reference's FlyingChairs crop on one of eight cards: its level 6 is 5 x 7 and takes the generic routes."""
     from maskflownet_amd import hotpath
     from oracle import hotpath_ref
     wl = hotpath.HotPathWorkload(cfg, device="cuda", mode=mode, seed=7)
