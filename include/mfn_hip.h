@@ -455,6 +455,33 @@ int mfn_batch_gather(const void *rows_dev, size_t rows_bytes, unsigned long long
                      unsigned char *img1, unsigned char *img2, float *label, unsigned char *mask, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * A validation batch read where the data set lies -- replaces what PipelineFlownet.validate of
+ * /root/reference/network/pipeline.py:149-187 does to a batch on the host around the network, and its uploads, for samples that are
+ * resident on the device as the readers store them.  rows_dev: N rows of a table made by mfn_batch_gather_build_rows, on the device
+ * (a window of a longer table is the address of its first row: rows are 64 bytes).  Every slot is the whole H x W sample: the caller
+ * has checked Hs == H, Ws == W, y0 == x0 == 0 and flip == 0 on its host copy; the kernels read the pointers and the label type only.
+ * READ CONTRACT: that of mfn_batch_gather.  kernels/validate.h names, for each entry, the operator whose bits it gives.
+ * Errors before any launch: a NULL table or tensor (MFN_E_NULL); N < 0, H, W, Hout or Wout < 1 (MFN_E_PARAM); a missing or short
+ * workspace (MFN_E_WORKSPACE); a table that is not 8-byte aligned, a float pointer that is not 4-byte aligned (MFN_E_ALIGN);
+ * N > 32767 or a sample of 2^31 bytes (MFN_E_UNSUPPORTED).  N == 0 succeeds and touches nothing. */
+/* rgb_mean of pipeline.py:86 on the bytes / 255 of :208 for the N slots' (img1, img2): exact integer sums, mean (N,3); the bits of
+ * mfn_pair_mean_u8 on the same bytes. */
+size_t mfn_val_pair_mean_workspace_bytes(int N, int H, int W);
+int mfn_val_pair_mean(const void *rows_dev, int N, int H, int W, float *mean, void *workspace, size_t workspace_bytes, void *stream);
+/* pipeline.py:208 (`/ 255`, HWC -> CHW), :120 and :129-130 in one launch: out (2N,3,Hout,Wout), image 1 of slot n in row n, image 2
+ * in row N + n; mean_or_null (N,3), NULL subtracts nothing; Hout == H and Wout == W unpacks.  The bits of mfn_preprocess_pair_u8 on
+ * the same bytes. */
+int mfn_val_preprocess(const void *rows_dev, int N, int H, int W, const float *mean_or_null, float *out, int Hout, int Wout,
+                       void *stream);
+/* pipeline.py:175-176 and :146, :182: the sums of mfn_flow_metrics, (N,3), of flow (N,2,H,W) in network order (channel 0 = dy)
+ * against each slot's stored HWC (u, v) label -- fp32, or fp16 widened exactly; channel 0 of the network order is the stored v -- under
+ * its mask (float)byte / 255.f, 1.f for a slot without one.  The reduction is mfn_flow_metrics's: the bits of that entry on the
+ * label and mask materialised as fp32 tensors. */
+size_t mfn_val_flow_metrics_workspace_bytes(int N, int H, int W);
+int mfn_val_flow_metrics(const void *rows_dev, const float *flow, int N, int H, int W, float *sums, void *workspace,
+                         size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Raw decoded KITTI / HD1K arrays turned into stored samples -- replaces what the reference's readers do to
  * every sample at load time on the host with cv2: /root/reference/reader/kitti.py:57-74 and reader/hd1k.py:51-78 (crop, HD1K's
  * min/max stretch, cv2.resize of the images, bilinear resize of flow and validity, flow re-scaling, the division by the resized

@@ -78,6 +78,12 @@ SIGNATURES = {
     "batch_gather_rows_bytes": (C.c_size_t, [_i]),
     "batch_gather_build_rows": (_i, [_i] + [C.POINTER(C.c_void_p)] * 4 + [_pi] * 6 + [_i, _i, C.c_void_p, C.c_size_t, C.POINTER(C.c_ulonglong)]),
     "batch_gather": (_i, [C.c_void_p, C.c_size_t, C.c_ulonglong] + [_i] * 4 + [C.c_void_p] * 4 + [_s]),
+    # a validation batch read through the rows of a resident data set (kernels/validate.h)
+    "val_pair_mean_workspace_bytes": (C.c_size_t, [_i] * 3),
+    "val_pair_mean": (_i, [C.c_void_p] + [_i] * 3 + [_f, C.c_void_p, C.c_size_t, _s]),
+    "val_preprocess": (_i, [C.c_void_p] + [_i] * 3 + [_f, _f, _i, _i, _s]),
+    "val_flow_metrics_workspace_bytes": (C.c_size_t, [_i] * 3),
+    "val_flow_metrics": (_i, [C.c_void_p, _f] + [_i] * 3 + [_f, C.c_void_p, C.c_size_t, _s]),
     # raw decoded arrays into stored samples (kernels/ingest.h); the tables entries and png_unfilter are host-only
     "ingest_tables_bytes": (C.c_size_t, [_i, _i]),
     "ingest_build_tables": (_i, [_i] * 4 + [C.c_void_p, C.c_size_t, C.POINTER(C.c_ulonglong)]),

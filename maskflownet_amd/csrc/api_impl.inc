@@ -24,6 +24,7 @@
 #include "kernels/loss.h"
 #include "kernels/optimizer.h"
 #include "kernels/batch.h"
+#include "kernels/validate.h"
 #include "kernels/ingest.h"
 #include "kernels/backward.h"
 #include "kernels/dc_backward.h"
@@ -2101,6 +2102,76 @@ int MFN_API(batch_gather)(const void *rows_dev, size_t rows_bytes, unsigned long
   p.N = N; p.Hc = Hc; p.Wc = Wc;
   p.label16 = aligned(label, 16) ? 1u : 0u;
   return hipfail(batch_gather_launch(p, (hipStream_t)stream), "batch_gather");
+}
+
+// ---- a validation batch read through the rows of a resident data set (kernels/validate.h) -----------------------------------------
+// what every validate entry accepts: a table for N >= 0 slots of H x W >= 1 x 1, inside what one launch indexes
+static int val_dims(const char *what, const void *rows, int N, int H, int W) {
+  if (N < 0) return fail(MFN_E_PARAM, "%s: N=%d is negative", what, N);
+  if (H < 1 || W < 1) return fail(MFN_E_PARAM, "%s: H=%d W=%d must be >= 1", what, H, W);
+  if (N > 32767 || (size_t)H * W * 3 >= ((size_t)1 << 31)) return fail(MFN_E_UNSUPPORTED, "%s: N=%d of %dx%d is more than one launch covers", what, N, H, W);
+  if (!aligned(rows, 8)) return fail(MFN_E_ALIGN, "%s: the table must be 8-byte aligned", what);
+  return 0;
+}
+
+size_t MFN_API(val_pair_mean_workspace_bytes)(int N, int H, int W) {
+  if (N <= 0 || H <= 0 || W <= 0) return 0;
+  return (size_t)N * pred_slices((size_t)2 * H * W) * 3 * sizeof(unsigned);
+}
+
+int MFN_API(val_pair_mean)(const void *rows_dev, int N, int H, int W, float *mean, void *workspace, size_t workspace_bytes, void *stream) {
+  if (N != 0 && (!rows_dev || !mean)) return fail(MFN_E_NULL, "val_pair_mean: NULL table or mean");
+  if (int rc = val_dims("val_pair_mean", rows_dev, N, H, W)) return rc;
+  if (N == 0) return 0;
+  const size_t plane = (size_t)H * W;
+  if (int rc = reduce_dims("val_pair_mean", (size_t)N, 2 * plane)) return rc;
+  const int slices = pred_slices(2 * plane);
+  const size_t need = (size_t)N * slices * 3 * sizeof(unsigned);
+  if (!workspace || workspace_bytes < need)
+    return fail(MFN_E_WORKSPACE, "val_pair_mean: workspace of %zu bytes needed, %zu given", need, workspace ? workspace_bytes : (size_t)0);
+  if (!aligned(workspace, 4) || !aligned(mean, 4)) return fail(MFN_E_ALIGN, "val_pair_mean: mean and workspace must be 4-byte aligned");
+  ValPairMeanParams p{(const BatchRow *)rows_dev,
+                      PairMeanU8Params{nullptr, (unsigned *)workspace, mean, plane, 255.0 * (double)(2 * plane), 0, 0, N, slices}};
+  return hipfail(val_pair_mean_launch(p, (hipStream_t)stream), "val_pair_mean");
+}
+
+int MFN_API(val_preprocess)(const void *rows_dev, int N, int H, int W, const float *mean_or_null, float *out, int Hout, int Wout,
+                            void *stream) {
+  if (N != 0 && (!rows_dev || !out)) return fail(MFN_E_NULL, "val_preprocess: NULL table or out");
+  if (int rc = val_dims("val_preprocess", rows_dev, N, H, W)) return rc;
+  if (Hout < 1 || Wout < 1) return fail(MFN_E_PARAM, "val_preprocess: Hout=%d Wout=%d must be >= 1", Hout, Wout);
+  if (int rc = resize_dims("val_preprocess", N, 3, H, W, Hout, Wout)) return rc;
+  if (N == 0) return 0;
+  if (!aligned(out, 4) || !aligned(mean_or_null, 4)) return fail(MFN_E_ALIGN, "val_preprocess: mean and out must be 4-byte aligned");
+  ValPreParams p{};
+  p.rows = (const BatchRow *)rows_dev; p.mean = mean_or_null; p.out = out;
+  p.N = N; p.H = H; p.W = W; p.Hout = Hout; p.Wout = Wout;
+  p.ry = Hout > 1 ? (float)(H - 1) / (float)(Hout - 1) : 0.f;
+  p.rx = Wout > 1 ? (float)(W - 1) / (float)(Wout - 1) : 0.f;
+  p.st_policy = store_policy_for(settings_now(), (size_t)6 * N * Hout * Wout * 4, 2, -1);
+  return hipfail(val_pre_launch(p, (hipStream_t)stream), "val_preprocess");
+}
+
+size_t MFN_API(val_flow_metrics_workspace_bytes)(int N, int H, int W) {
+  if (N <= 0 || H <= 0 || W <= 0) return 0;
+  return (size_t)N * pred_slices((size_t)H * W) * 3 * sizeof(float);
+}
+
+int MFN_API(val_flow_metrics)(const void *rows_dev, const float *flow, int N, int H, int W, float *sums, void *workspace,
+                              size_t workspace_bytes, void *stream) {
+  if (N != 0 && (!rows_dev || !flow || !sums)) return fail(MFN_E_NULL, "val_flow_metrics: NULL table, flow or sums");
+  if (int rc = val_dims("val_flow_metrics", rows_dev, N, H, W)) return rc;
+  if (N == 0) return 0;
+  const size_t plane = (size_t)H * W;
+  if (int rc = reduce_dims("val_flow_metrics", N, plane)) return rc;
+  const int slices = pred_slices(plane);
+  const size_t need = (size_t)N * slices * 3 * sizeof(float);
+  if (!workspace || workspace_bytes < need)
+    return fail(MFN_E_WORKSPACE, "val_flow_metrics: workspace of %zu bytes needed, %zu given", need, workspace ? workspace_bytes : (size_t)0);
+  if (!aligned(workspace, 4) || !aligned(flow, 4) || !aligned(sums, 4))
+    return fail(MFN_E_ALIGN, "val_flow_metrics: flow, sums and workspace must be 4-byte aligned");
+  ValMetricsParams p{(const BatchRow *)rows_dev, FlowMetricsParams{flow, nullptr, nullptr, (float *)workspace, sums, plane, N, slices}};
+  return hipfail(val_flow_metrics_launch(p, (hipStream_t)stream), "val_flow_metrics");
 }
 
 // ---- raw decoded arrays into stored samples (kernels/ingest.h) -------------------------------------------------------------------

@@ -206,32 +206,38 @@ struct FlowMetricsParams {
   size_t plane;
   int N, slices;
 };
+// one pixel's terms of the three sums: flow (fy, fx), label (ly, lx), mask m.  The one statement of this arithmetic: every kernel
+// that makes these sums (here and in validate.h) adds its pixels through it, in the same order, and so gives the same bits.
+__device__ __forceinline__ void flow_metrics_term(float fy, float fx, float ly, float lx, float m, float &s0, float &s1, float &s2) {
+  const float eps = 1e-8f;
+  const float dy = fy - ly, dx = fx - lx;
+  const float sq = dy * dy + dx * dx;
+  const float nd = sqrtf(sq), nl = sqrtf(ly * ly + lx * lx);
+  s0 += m * sqrtf(sq + eps);
+  s1 += m;
+  s2 += (nd > 3.f && nd / (nl + eps) > 0.05f) ? m : 0.f;
+}
+// the block's three sums joined, one tree per sum, each on its own 256 floats: -> partial[0..3)
+__device__ __forceinline__ void flow_metrics_block_sums(float *red, float s0, float s1, float s2, float *partial) {
+  float s[3] = {s0, s1, s2};
+  for (int j = 0; j < 3; ++j) {
+    red[j * 256 + threadIdx.x] = s[j];
+    pred_block_tree(red + j * 256);
+  }
+  if (threadIdx.x < 3) partial[threadIdx.x] = red[threadIdx.x * 256];
+}
 __global__ __launch_bounds__(256) void flow_metrics_partial_kernel(FlowMetricsParams p) {
   MFN_DYN_SHARED(float, red);   // [3][256]
   const int sl = blockIdx.x, n = blockIdx.y;
   const float *f = p.flow + (size_t)n * 2 * p.plane, *l = p.label + (size_t)n * 2 * p.plane, *mk = p.mask + (size_t)n * p.plane;
   const size_t base = (size_t)sl * PRED_SLICE;
-  const float eps = 1e-8f;
   float s0 = 0.f, s1 = 0.f, s2 = 0.f;
   MFN_UNROLL
   for (int k = 0; k < PRED_RUN; ++k) {
     const size_t q = base + (size_t)k * 256 + threadIdx.x;
-    if (q < p.plane) {
-      const float dy = f[q] - l[q], dx = f[p.plane + q] - l[p.plane + q];
-      const float ly = l[q], lx = l[p.plane + q], m = mk[q];
-      const float sq = dy * dy + dx * dx;
-      const float nd = sqrtf(sq), nl = sqrtf(ly * ly + lx * lx);
-      s0 += m * sqrtf(sq + eps);
-      s1 += m;
-      s2 += (nd > 3.f && nd / (nl + eps) > 0.05f) ? m : 0.f;
-    }
+    if (q < p.plane) flow_metrics_term(f[q], f[p.plane + q], l[q], l[p.plane + q], mk[q], s0, s1, s2);
   }
-  float s[3] = {s0, s1, s2};
-  for (int j = 0; j < 3; ++j) {   // one tree per sum, each on its own 256 floats
-    red[j * 256 + threadIdx.x] = s[j];
-    pred_block_tree(red + j * 256);
-  }
-  if (threadIdx.x < 3) p.partial[((size_t)n * p.slices + sl) * 3 + threadIdx.x] = red[threadIdx.x * 256];
+  flow_metrics_block_sums(red, s0, s1, s2, p.partial + ((size_t)n * p.slices + sl) * 3);
 }
 __global__ __launch_bounds__(256) void flow_metrics_final_kernel(FlowMetricsParams p) {
   MFN_DYN_SHARED(float, red);

@@ -139,6 +139,7 @@ class MaskFlownetS:
         self.graph = None
         self.lib = _lib.lib()
         self._packed = {}
+        self._packers = {}    # key of _packed -> the pack call that made it, taking the destination
         self._flops = {}
         self.b = {}     # named, preallocated device buffers
         N = self.N
@@ -189,12 +190,12 @@ class MaskFlownetS:
             self._flops[name] = 2.0 * out.shape[0] * out.shape[2] * out.shape[3] * x.shape[1] * out.shape[1] * (4 if transposed else 9)
         if transposed:
             if pk is None:
-                pk = self._packed[key] = self.ops.pack_conv_weights(w, tuple(x.shape), kernel=(4, 4), stride=(2, 2), pad=(1, 1), transposed=True)
+                pk = self._pack(key, self.ops.pack_conv_weights, name, tuple(x.shape), kernel=(4, 4), stride=(2, 2), pad=(1, 1), transposed=True)
             return self.ops.Deconvolution(x, w, b, kernel=(4, 4), stride=(2, 2), pad=(1, 1), out=out,
                                           activation="leaky" if act else None, packed=pk)
         if pk is None:
-            pk = self._packed[key] = self.ops.pack_conv_weights(w, tuple(x.shape), kernel=(3, 3), stride=(stride, stride),
-                                                                dilate=(dilation, dilation), pad=(dilation, dilation))
+            pk = self._pack(key, self.ops.pack_conv_weights, name, tuple(x.shape), kernel=(3, 3), stride=(stride, stride),
+                            dilate=(dilation, dilation), pad=(dilation, dilation))
         return self.ops.Convolution(x, w, b, kernel=(3, 3), stride=(stride, stride), dilate=(dilation, dilation),
                                     pad=(dilation, dilation), out=out, activation="leaky" if act else None, packed=pk)
 
@@ -255,8 +256,52 @@ class MaskFlownetS:
         key = (name, tuple(x.shape))
         pk = self._packed.get(key)
         if pk is None:
-            pk = self._packed[key] = self.ops.pack_deform_weights(self.P[name + ".weight"], tuple(x.shape), kernel=(3, 3), pad=(1, 1))
+            pk = self._pack(key, self.ops.pack_deform_weights, name, tuple(x.shape), kernel=(3, 3), pad=(1, 1))
         return pk
+
+    def _pack(self, key, packer, name, shape, **kw):
+        """Pack P[name.weight] for inputs of `shape` and remember the call: load_weights makes it again into the same buffer."""
+        self._packers[key] = lambda out: packer(self.P[name + ".weight"], shape, out=out, **kw)
+        pk = self._packed[key] = self._packers[key](None)
+        return pk
+
+    # ---- new weights under the captured graph -------------------------------------------------------------------------------
+    def _slot(self, key):
+        """The name in self.P of the constructor's parameter `key`."""
+        return key
+
+    def load_weights(self, params):
+        """Replace every parameter by params[name] (the constructor's keys; tensors on any device, or arrays) IN PLACE, on
+        self.stream: copy_ into the tensors of self.P, the fused heads concatenated again into theirs, every packed layout written
+        again into its buffer.  No address changes, so a captured graph runs the new weights at its next replay.  Unknown, missing
+        or mis-shaped keys raise before anything is written; a pack that answers with another layout tag than at capture (tuning or
+        arithmetic changed since) raises.  Does not synchronise."""
+        t = self.torch
+        slots = {self._slot(k): k for k in params}
+        own = [k for k in self.P if not k.split("/")[-1].startswith("heads")]
+        unknown = sorted(k for s, k in slots.items() if s not in own)
+        missing = sorted(s for s in own if s not in slots)
+        if unknown or missing or len(slots) != len(params):
+            raise KeyError("load_weights: unknown keys %s, missing keys %s" % (unknown[:4], missing[:4]))
+        src = {}
+        for s, k in slots.items():
+            v = params[k]
+            v = v.detach() if isinstance(v, t.Tensor) else t.from_numpy(np.ascontiguousarray(v, dtype=np.float32))
+            if tuple(v.shape) != tuple(self.P[s].shape):
+                raise ValueError("load_weights: %s has shape %s, expected %s" % (k, tuple(v.shape), tuple(self.P[s].shape)))
+            src[s] = v
+        with t.cuda.stream(self.stream):
+            for s, v in src.items():
+                self.P[s].copy_(v, non_blocking=True)
+            for l in (6, 5, 4, 3):
+                for part in ("weight", "bias"):
+                    t.cat([self.P["pred_flow%d.%s" % (l, part)], self.P["pred_mask%d.%s" % (l, part)]], out=self.P["heads%d.%s" % (l, part)])
+            for key, pk in self._packed.items():
+                again = self._packers[key](pk)
+                if again.tag != pk.tag or again.buf.data_ptr() != pk.buf.data_ptr():
+                    raise RuntimeError("load_weights: %s packs to layout %x now, the captured graph reads layout %x: tuning or arithmetic "
+                                       "changed since capture" % (key[0], again.tag, pk.tag))
+        return self
 
     # ---- running it ------------------------------------------------------------------------------------------------------
     def set_input(self, im1, im2):
@@ -362,6 +407,9 @@ class MaskFlownet(MaskFlownetS):
             b["gflow_full"] = e(N, 2, H, W)
         self.stream.synchronize()
         torch.cuda.synchronize(self.dev)
+
+    def _slot(self, key):
+        return key[len(HEAD):] if key.startswith(HEAD) else CASCADE + key
 
     def _forward(self):
         super()._forward()

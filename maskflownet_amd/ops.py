@@ -297,10 +297,11 @@ class OpSet:
         return out
 
     def pack_deform_weights(self, weight, data_shape, kernel=(3, 3), stride=(1, 1), dilate=(1, 1), pad=(0, 0),
-                            num_group=1, num_deformable_group=1):
+                            num_group=1, num_deformable_group=1, out=None):
         """Lay constant DeformableConvolution weights out once for inputs of `data_shape` (N,Cin,H,W);
         mfn_deform_conv_pack_weights.  The layout depends on the shape and on set_tuning(): re-pack after
-        changing either (a stale pack is refused, never silently used)."""
+        changing either (a stale pack is refused, never silently used).  out: a PackedDeformWeights of the same dims whose
+        buffer is written again (new weights at an address a captured graph holds)."""
         (w,) = self._in(weight)
         (kh, kw), (sh, sw), (ph, pw), (dh, dw) = map(self._pair, (kernel, stride, pad, dilate))
         N, Cin, H, W = (int(v) for v in data_shape)
@@ -312,7 +313,7 @@ class OpSet:
         nbytes = self.ns.deform_conv_packed_weight_bytes(*dims)
         if not nbytes:
             raise ValueError("pack_deform_weights: bad shape %s" % (dims,))
-        buf = self.ad.empty_bytes(w, nbytes)
+        buf = self._pack_buffer(w, nbytes, dims, out, "pack_deform_weights")
         tag = ctypes.c_ulonglong()
         self.check(self.ns.deform_conv_pack_weights(self.ad.ptr(w), *dims, self.ad.ptr(buf), nbytes,
                                                     ctypes.byref(tag), self.ad.stream(w)))
@@ -788,7 +789,7 @@ class OpSet:
         self.check(self.ns.batch_gather_build_rows(N, *cols, ints(Hs), ints(Ws), ints(lt), ints([o[0] for o in origins]),
                                                    ints([o[1] for o in origins]), ints(flips), Hc, Wc, ctypes.addressof(host), nbytes,
                                                    ctypes.byref(tag)))
-        return BatchRows(self._upload(samples[0][0], host, nbytes), nbytes, tag.value, N, (Hc, Wc), samples)
+        return BatchRows(self._upload(samples[0][0], host, nbytes), nbytes, tag.value, N, (Hc, Wc), samples, origins, flips)
 
     def batch_gather(self, rows, crop_shape, with_mask, out=None):
         """One batch in one launch (mfn_batch_gather): -> (img1, img2 (N,3,Hc,Wc) uint8, label (N,2,Hc,Wc) float32 in the readers' (u, v)
@@ -823,6 +824,71 @@ class OpSet:
                                         self.ad.ptr(i2), self.ad.ptr(lab), self.ad.ptr(msk) if with_mask else None,
                                         self.ad.stream(rows.buf)))
         return i1, i2, lab, (msk if with_mask else None)
+
+    # ---- a validation batch read through the rows of a resident data set (pipeline.py:149-187; kernels/validate.h) -------------------
+    def _val_rows(self, rows, first, n, what):
+        """The window [first, first + n) of a table of batch_gather_rows, checked on the host before any launch: every slot the whole
+        (H, W) sample, unflipped.  -> (address of row `first`, H, W)."""
+        if not isinstance(rows, BatchRows):
+            raise TypeError("%s: rows must come from batch_gather_rows, got %r" % (what, type(rows)))
+        if getattr(rows.buf, "is_cuda", True) is False:
+            raise RuntimeError("maskflownet_amd ops run on the MI355X only: %s: the table is on %s (there is no CPU fallback)"
+                               % (what, rows.buf.device))
+        first, n = int(first), int(n)
+        if first < 0 or n < 0 or first + n > rows.N:
+            raise ValueError("%s: rows [%d, %d) leave a table of %d" % (what, first, first + n, rows.N))
+        if len(rows.origins) != rows.N or len(rows.flips) != rows.N:
+            raise ValueError("%s: the table carries no host copy of its origins and flips" % what)
+        H, W = rows.crop_shape
+        for k in range(first, first + n):
+            shp = tuple(int(v) for v in self.ad.shape(rows.samples[k][0])[:2])
+            if shp != (H, W) or rows.origins[k] != (0, 0) or rows.flips[k] != 0:
+                raise ValueError("%s: row %d is a %dx%d crop at %s%s of a %dx%d sample; a validation slot is the whole sample, unflipped"
+                                 % (what, k, H, W, rows.origins[k], " flipped" if rows.flips[k] else "", shp[0], shp[1]))
+        return self.ad.ptr(rows.buf) + first * BatchRows.ROW_BYTES, H, W
+
+    def val_pair_mean(self, rows, first, n, out=None):
+        """pair_mean_u8 for the n slots from row `first` of a table of batch_gather_rows, read where the samples lie: rgb_mean of
+        pipeline.py:86 on bytes / 255 -> (n,3), exact; the bits of pair_mean_u8 on the same images (mfn_val_pair_mean)."""
+        what = "val_pair_mean"
+        table, H, W = self._val_rows(rows, first, n, what)
+        n = int(n)
+        out = self._out(out, rows.buf, (n, 3), what)
+        ws = self._workspace(rows.buf, self.ns.val_pair_mean_workspace_bytes(n, H, W))
+        self.check(self.ns.val_pair_mean(table, n, H, W, self.ad.ptr(out), self.ad.ptr(ws), self.ad.nbytes(ws), self.ad.stream(rows.buf)))
+        return out
+
+    def val_preprocess(self, rows, first, n, height, width, mean=None, out=None):
+        """preprocess_pair_u8 for those slots (pipeline.py:208, :120-130): -> (2n,3,height,width), image 1 of slot k in row k, image 2 in
+        row n + k; the bits of preprocess_pair_u8 on the same images.  mean (n,3): subtracted from every tap; None subtracts nothing."""
+        what = "val_preprocess"
+        table, H, W = self._val_rows(rows, first, n, what)
+        n = int(n)
+        m = None
+        if mean is not None:
+            (m,) = self._in(mean)
+            if self.ad.shape(m) != (n, 3):
+                raise ValueError("%s: mean must have shape %s, got %s" % (what, (n, 3), self.ad.shape(m)))
+        out = self._out(out, rows.buf, (2 * n, 3, int(height), int(width)), what)
+        self.check(self.ns.val_preprocess(table, n, H, W, self.ad.ptr(m) if m is not None else None, self.ad.ptr(out), int(height),
+                                          int(width), self.ad.stream(rows.buf)))
+        return out
+
+    def val_flow_metric_sums(self, rows, first, n, flow, out=None):
+        """flow_metric_sums of flow (n,2,H,W), network order, against those slots' stored labels and masks (pipeline.py:175-176, :146,
+        :182): the label's (u, v) flipped to (dy, dx), fp16 widened exactly, the mask byte / 255 (all valid without one) -> (n,3); the
+        bits of flow_metric_sums on the materialised fp32 tensors (mfn_val_flow_metrics)."""
+        what = "val_flow_metric_sums"
+        table, H, W = self._val_rows(rows, first, n, what)
+        n = int(n)
+        (f,) = self._in(flow)
+        if self.ad.shape(f) != (n, 2, H, W):
+            raise ValueError("%s: flow must have shape %s, got %s" % (what, (n, 2, H, W), self.ad.shape(f)))
+        out = self._out(out, f, (n, 3), what)
+        ws = self._workspace(f, self.ns.val_flow_metrics_workspace_bytes(n, H, W))
+        self.check(self.ns.val_flow_metrics(table, self.ad.ptr(f), n, H, W, self.ad.ptr(out), self.ad.ptr(ws), self.ad.nbytes(ws),
+                                            self.ad.stream(f)))
+        return out
 
     # ---- raw decoded KITTI / HD1K arrays into stored samples (reader/kitti.py:57-74, reader/hd1k.py:51-78) ---------------------------
     _INGEST_FLOW = {"float32": 0, "float16": 1}
@@ -1187,9 +1253,21 @@ class OpSet:
         return self._conv("Deconvolution", True, data, weight, bias, kernel, stride, dilate, pad, adj, num_filter, num_group,
                           no_bias, out, activation, packed)
 
+    def _pack_buffer(self, like, nbytes, dims, out, what):
+        """Where a pack entry writes: a fresh buffer, or the one of `out`, which must have been laid out for the same dims."""
+        if out is None:
+            return self.ad.empty_bytes(like, nbytes)
+        if not isinstance(out, PackedDeformWeights):
+            raise TypeError("%s: out must be a PackedDeformWeights, got %r" % (what, type(out)))
+        out.require(dims)
+        if out.nbytes != int(nbytes):
+            raise ValueError("%s: out holds %d bytes, this layout takes %d (tuning changed since it was packed)" % (what, out.nbytes, nbytes))
+        return out.buf
+
     def pack_conv_weights(self, weight, data_shape, kernel=(3, 3), stride=(1, 1), dilate=(1, 1), pad=(0, 0), num_group=1,
-                          transposed=False):
-        """Lay constant Convolution / Deconvolution weights out once for inputs of `data_shape` (mfn_conv2d_pack_weights)."""
+                          transposed=False, out=None):
+        """Lay constant Convolution / Deconvolution weights out once for inputs of `data_shape` (mfn_conv2d_pack_weights).  out: as
+        pack_deform_weights."""
         (w,) = self._in(weight)
         (kh, kw), (sh, sw), (ph, pw), (dh, dw) = map(self._pair, (kernel, stride, pad, dilate))
         N, Cin, H, W = (int(v) for v in data_shape)
@@ -1199,7 +1277,7 @@ class OpSet:
         nbytes = self.ns.conv2d_packed_weight_bytes(*dims)
         if not nbytes:
             raise ValueError("pack_conv_weights: bad shape %s" % (dims,))
-        buf = self.ad.empty_bytes(w, nbytes)
+        buf = self._pack_buffer(w, nbytes, dims, out, "pack_conv_weights")
         tag = ctypes.c_ulonglong()
         self.check(self.ns.conv2d_pack_weights(self.ad.ptr(w), *dims, self.ad.ptr(buf), nbytes, ctypes.byref(tag),
                                                self.ad.stream(w)))
@@ -1242,11 +1320,14 @@ class AdamTable:
 
 class BatchRows:
     """Opaque device table made by OpSet.batch_gather_rows: one 64-byte row per batch slot and the tag that binds it to (N, Hc, Wc).
-    It holds addresses: `samples` keeps the sources alive as long as the table is."""
+    It holds addresses: `samples` keeps the sources alive as long as the table is.  `origins` and `flips` are the host's copy of what the
+    rows say: the validate ops check a window of the table against them before any launch."""
+    ROW_BYTES = 64
 
-    def __init__(self, buf, nbytes, tag, N, crop_shape, samples):
+    def __init__(self, buf, nbytes, tag, N, crop_shape, samples, origins=(), flips=()):
         self.buf, self.nbytes, self.tag, self.N, self.crop_shape = buf, int(nbytes), int(tag), int(N), tuple(crop_shape)
         self.samples = list(samples)
+        self.origins, self.flips = [(int(o[0]), int(o[1])) for o in origins], [int(f) for f in flips]
 
 
 class IngestTables:
@@ -1428,6 +1509,18 @@ def batch_gather_rows(*a, **k):
 
 def batch_gather(*a, **k):
     return default_ops().batch_gather(*a, **k)
+
+
+def val_pair_mean(*a, **k):
+    return default_ops().val_pair_mean(*a, **k)
+
+
+def val_preprocess(*a, **k):
+    return default_ops().val_preprocess(*a, **k)
+
+
+def val_flow_metric_sums(*a, **k):
+    return default_ops().val_flow_metric_sums(*a, **k)
 
 
 def ingest_tables(*a, **k):

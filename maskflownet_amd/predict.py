@@ -18,6 +18,8 @@ stay bytes until they are on the device: `do_batch_u8` / `predict_frames` upload
 and the network's input batch straight from the bytes (csrc/kernels/frames.h) and can colour the flows there
 (flow_vis.flow_to_color, restated and unpinned); `python -m maskflownet_amd.predict` is the command line on top of them.
 """
+import weakref
+
 import numpy as np
 
 from . import network
@@ -64,6 +66,7 @@ class Predictor:
         self.net = (network.MaskFlownet if full else network.MaskFlownetS)(params, self.N, self.H64, self.W64, device)
         self.dev, self.stream = self.net.dev, self.net.stream
         self.frames_uploaded = 0            # frames that predict_frames sent to the device: one per frame of the sequence
+        self._val_key, self._val_ds = None, lambda: None      # validate_dataset's table: which set and selection it was built for
         N, H, W = self.N, self.H, self.W
         with torch.cuda.stream(self.stream):
             e = lambda *shape: torch.empty(*shape, device=self.dev)
@@ -273,6 +276,66 @@ class Predictor:
             out = self.do_batch(np.stack([_chw01(a) for a in im1]), np.stack([_chw01(a) for a in im2]), lab, m)
             vals.append((out["epe"] if return_type == "epe" else out["fl"]).cpu().numpy())
         return float(np.mean(np.concatenate(vals)))
+
+    # ---- validation during training: the net being trained, on a data set that is resident on the device ---------------------------
+    def load_weights(self, named_params, wait_stream=None):
+        """The network's weights replaced in place under its captured graph (network.MaskFlownetS.load_weights): no allocation, no
+        capture.  named_params: a dict, or (name, parameter) pairs as training.reference_named_parameters returns them; device
+        tensors are read where they are.  wait_stream (default: the device's current stream) is the stream whose work wrote them --
+        the optimizer step: an event recorded there is waited for by the network's stream before the first copy.  Does not
+        synchronise: anything that overwrites the parameters next must be ordered behind the network's stream (validate_dataset
+        returns after a synchronisation)."""
+        t = self.torch
+        params = dict(named_params)
+        ev = t.cuda.Event()
+        ev.record(wait_stream if wait_stream is not None else t.cuda.current_stream(self.dev))
+        self.stream.wait_event(ev)
+        self.net.load_weights(params)
+        return self
+
+    def _val_table(self, ds, indices):
+        """One table for the whole set: ceil(S / N) * N rows, the short last batch padded with its last row; uploaded once and kept
+        while the data set and the selection stay the same."""
+        idx = tuple(range(len(ds))) if indices is None else tuple(int(i) for i in indices)
+        if not idx:
+            raise ValueError("validate_dataset: no samples")
+        key = (id(ds), idx)
+        if self._val_key != key or self._val_ds() is not ds:
+            for i in idx:
+                if ds.shape(i) != (self.H, self.W):
+                    raise ValueError("validate_dataset: sample %d is %dx%d, this Predictor was built for %dx%d" % ((i,) + ds.shape(i) + (self.H, self.W)))
+            pad = idx + idx[-1:] * (-len(idx) % self.N)
+            samples = [ds.sample(i) for i in pad]
+            with self.torch.cuda.stream(self.stream):
+                rows = self.ops.batch_gather_rows(samples, (self.H, self.W), [(0, 0)] * len(pad), [0] * len(pad))
+                sums = self.torch.empty(len(idx), 3, device=self.dev)
+            self._val_key, self._val_ds, self._val_rows, self._val_sums = key, weakref.ref(ds), rows, sums
+        return len(idx), self._val_rows, self._val_sums
+
+    def validate_dataset(self, ds, indices=None):
+        """PipelineFlownet.validate (pipeline.py:149-187) over the samples `indices` (default: all) of a data.DeviceDataset whose
+        samples have this Predictor's (H, W), without a host copy of any of them: per batch the joint mean, the network's input batch,
+        one replay, the way back to (H, W) and the metric sums of the batch's slots are enqueued on the network's stream, reading
+        images, labels (flipped to (dy, dx), :176) and masks (/ 255, :175; all valid where the set has none) where they lie
+        (kernels/validate.h).  The warp is skipped: validate never reads it.  One synchronisation and one (S,3) download per set.
+        -> {"epe", "fl": the set's means as floats, "per_sample": (S,2) float32 numpy of (epe, fl)}."""
+        t, ops, b, net, N = self.torch, self.ops, self.b, self.net, self.N
+        S, rows, sums = self._val_table(ds, indices)
+        self.stream.wait_stream(t.cuda.current_stream(self.dev))      # the data set's uploads and ingest kernels were enqueued there
+        with t.cuda.stream(self.stream):
+            for j in range(0, S, N):
+                n = min(N, S - j)
+                ops.val_pair_mean(rows, j, N, out=b["mean"])                                   # pipeline.py:86 on bytes / 255 (:208)
+                ops.val_preprocess(rows, j, N, self.H64, self.W64, mean=b["mean"], out=net.b["im"])   # :120-130
+                net.replay()
+                flow = net.b["gflow_full" if self.full else "flow_full"]                       # Upsample(4)(flows[-1]), :137
+                if self.resized:                                                               # :139-141
+                    flow = ops.bilinear_resize(flow, self.H, self.W, flow_rescale=True, out=b["flow"])
+                ops.val_flow_metric_sums(rows, j, n, flow[:n], out=sums[j:j + n])              # :175-182
+            per = t.stack([sums[:, 0] / sums[:, 1], sums[:, 2] / sums[:, 1]], dim=1)
+        self.stream.synchronize()
+        per = per.cpu().numpy()
+        return {"epe": float(np.mean(per[:, 0])), "fl": float(np.mean(per[:, 1])), "per_sample": per}
 
 
 # ---- command line: the reference's predict_new_data.py for an image pair or a directory of frames ---------------------------------

@@ -605,3 +605,46 @@ def train_batch(net, loss_fn, opt, img1, img2, label, mask, geo_aug, color_aug, 
         hook.remove()
     epe, _ = ops.flow_metrics(ops.Upsample(finest[-1], loss_fn.scales[-1]), lab, msk)
     return loss, epe
+
+
+class Validation:
+    """`validation_datasets` of the reference's main.py:193-362 and the body of its `validate()` (:157-161), for sets that are resident
+    on the device: Validation(sets, batch, full=False, resize=None) with sets = {name: data.DeviceDataset}.  One predict.Predictor is
+    kept per distinct sample shape -- built, packed and captured at the first run that meets the shape; every later run puts the
+    net's current weights under its captured graph in place (Predictor.load_weights) and validates every set where it lies
+    (Predictor.validate_dataset).  full: the net is a MaskFlownetTrainable (frozen head and cascade), else a MaskFlownetSTrainable."""
+
+    def __init__(self, sets, batch, full=False, resize=None):
+        self.sets, self.batch, self.full, self.resize = dict(sets), int(batch), bool(full), resize
+        self.predictors = {}      # (H, W) -> Predictor
+
+    def run(self, net, kitti=False):
+        """-> {name: epe}, or {name: {"epe", "fl"}} with kitti=True (pipeline.py:183-187's two return types), for the net as it is now.
+        The weights are read behind the work enqueued on the current stream (the optimizer step) and every set is finished when this
+        returns, so the caller may step the optimizer at once."""
+        from .predict import Predictor
+        named = dict(reference_named_parameters(net))
+        groups = {}               # name -> {(H, W): [indices]}
+        for name, ds in self.sets.items():
+            by_shape = groups.setdefault(name, {})
+            for i in range(len(ds)):
+                by_shape.setdefault(ds.shape(i), []).append(i)
+        fresh = set()
+        for name, by_shape in groups.items():
+            for shape in by_shape:
+                if shape not in self.predictors:
+                    host = {k: p.detach().to("cpu", torch.float32).numpy() for k, p in named.items()}
+                    self.predictors[shape] = Predictor(host, self.batch, shape[0], shape[1], full=self.full, resize=self.resize,
+                                                       device=self.sets[name].device)
+                    fresh.add(shape)
+        for shape, p in self.predictors.items():
+            if shape not in fresh:
+                p.load_weights(named)
+        out = {}
+        for name, by_shape in groups.items():
+            per = np.zeros((len(self.sets[name]), 2), np.float32)
+            for shape, idx in by_shape.items():
+                per[idx] = self.predictors[shape].validate_dataset(self.sets[name], idx)["per_sample"]
+            epe, fl = float(np.mean(per[:, 0])), float(np.mean(per[:, 1]))
+            out[name] = {"epe": epe, "fl": fl} if kitti else epe
+        return out
