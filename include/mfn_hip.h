@@ -263,6 +263,34 @@ int mfn_upsample_bwd(const float *gout, float *gx, int N, int C, int H, int W, i
  * activations (mfn_correlation_fwd_act, mfn_conv2d_fwd activation = MFN_ACT_LEAKY_0_1; nn.LeakyReLU(0.1) of
  * /root/reference/network/MaskFlownet.py:76,217).  gin may alias gout. */
 int mfn_leaky_relu_bwd(const float *gout, const float *y, float *gin, size_t n, float slope, void *stream);
+/* The gate of the matching module on its own, for training through a pyramid level (kernels/gate.h) -- replaces
+ * network/MaskFlownet.py:231-233 (and :249-251, :267-269, :285-287), the part of mfn_deform_conv_matching_fwd after the
+ * deformable convolution, whose output `raw` the backward pass needs:
+ *   out = act(raw * s + tradeoff),  s = 1 / (1 + expf(-mask))
+ * raw, tradeoff, out: (N,C,H,W); mask: (N,1,H,W); mask and tradeoff each optional; activation: MFN_ACT_*.  Per element the
+ * arithmetic of mfn_deform_conv_matching_fwd's epilogue (the same device function).
+ * Backward, from g = gout (+ gout2: an optional second upstream gradient, added first), the forward OUTPUT y, raw and mask:
+ *   gp        = activation ? g * (y > 0 ? 1 : 0.1) : g                 (the rule of mfn_leaky_relu_bwd)
+ *   gtradeoff = gp
+ *   graw      = gp * s                                                  (gp without a mask)
+ *   gmask     = s * s' * sum_c gp[n,c,h,w] * raw[n,c,h,w],   s' = 1 / (1 + expf(+mask)), evaluated on its own (not 1 - s:
+ *               no bit of that is right on a saturated mask)
+ * req_* per output (MFN_REQ_NULL skips it and the pointer may be NULL); req_mask other than null without a mask is
+ * MFN_E_PARAM.  y is read with MFN_ACT_LEAKY_0_1 only, raw for gmask only: either may be NULL otherwise.  All three reqs
+ * null, or N == 0: nothing is launched.
+ * Deterministic: the channel sum of gmask is added in a fixed order that depends on (N, C, H, W) alone, without atomics --
+ * bit-identical from call to call.  Levels with few pixels split the channels over blocks; their partial sums need
+ * mfn_matching_gate_bwd_workspace_bytes of scratch (0 where one block row per image suffices) when req_mask is not null: a
+ * shorter workspace is MFN_E_WORKSPACE before any launch, there is no other route.  16-byte loads and stores where
+ * W % 4 == 0 and every pointer is 16-byte aligned, scalar ones otherwise; same results.  No output may alias an input or
+ * another output. */
+int mfn_matching_gate_fwd(const float *raw, const float *mask_or_null, const float *tradeoff_or_null, int activation,
+                          float *out, int N, int C, int H, int W, void *stream);
+size_t mfn_matching_gate_bwd_workspace_bytes(int N, int C, int H, int W);
+int mfn_matching_gate_bwd(const float *gout, const float *gout2_or_null, const float *y, const float *raw,
+                          const float *mask_or_null, int activation, float *graw, float *gmask, float *gtradeoff,
+                          int N, int C, int H, int W, int req_raw, int req_mask, int req_tradeoff,
+                          void *workspace, size_t workspace_bytes, void *stream);
 /* Offset builder of /root/reference/network/MaskFlownet.py:230:
  *   offset[n, 2k+t, y, x] = flow_yx[n, t, y, x] * scale / stride   for k < taps. */
 int mfn_offsets_from_flow(const float *flow_yx, float *offset, int N, int H, int W, int taps,

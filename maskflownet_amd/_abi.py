@@ -55,6 +55,10 @@ SIGNATURES = {
     "conv2d_fwd": (_i, [_f, C.c_longlong, _f, C.c_void_p, C.c_size_t, C.c_ulonglong, _f, _f, C.c_longlong] + [_i] * 18 + [C.c_void_p, C.c_size_t, _s]),
     "upsample_bwd": (_i, [_f, _f] + [_i] * 6 + [_s]),
     "leaky_relu_bwd": (_i, [_f, _f, _f, C.c_size_t, C.c_float, _s]),
+    # the matching module's gate on its own, forward and backward (kernels/gate.h)
+    "matching_gate_fwd": (_i, [_f, _f, _f, _i, _f] + [_i] * 4 + [_s]),
+    "matching_gate_bwd_workspace_bytes": (C.c_size_t, [_i] * 4),
+    "matching_gate_bwd": (_i, [_f] * 5 + [_i] + [_f] * 3 + [_i] * 7 + [C.c_void_p, C.c_size_t, _s]),
     "conv2d_bwd_workspace_bytes": (C.c_size_t, [_i] * 18),
     "conv2d_bwd": (_i, [_f] * 7 + [_i] * 21 + [C.c_void_p, C.c_size_t, _s]),
     # augmentation of the training batch (kernels/augment.h); bound by the emulation build as well

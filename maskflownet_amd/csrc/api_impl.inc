@@ -4,6 +4,7 @@
 // MFN_API(name) expands to the exported symbol.
 
 #include <atomic>
+#include <initializer_list>
 #include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -22,6 +23,7 @@
 #include "kernels/frames.h"
 #include "kernels/augment.h"
 #include "kernels/loss.h"
+#include "kernels/gate.h"
 #include "kernels/optimizer.h"
 #include "kernels/batch.h"
 #include "kernels/validate.h"
@@ -2276,6 +2278,61 @@ int MFN_API(png_unfilter)(unsigned char *raw, long long rows, long long row_byte
 int MFN_API(leaky_relu_bwd)(const float *gout, const float *y, float *gin, size_t n, float slope, void *stream) {
   if (n != 0 && (!gout || !y || !gin)) return fail(MFN_E_NULL, "leaky_relu_bwd: NULL tensor pointer");
   return hipfail(leaky_bwd_launch(LeakyBwdParams{gout, y, gin, n, slope}, (hipStream_t)stream), "leaky_relu_bwd");
+}
+
+// ---- the matching module's gate, forward and backward (kernels/gate.h) ---------------------------------------------------------
+static int gate_dims(const char *what, int N, int C, int H, int W, int activation) {
+  if (N < 0 || C <= 0 || H <= 0 || W <= 0) return fail(MFN_E_SHAPE, "%s: N=%d C=%d H=%d W=%d", what, N, C, H, W);
+  if (activation != MFN_ACT_NONE && activation != MFN_ACT_LEAKY_0_1) return fail(MFN_E_PARAM, "%s: activation=%d", what, activation);
+  if (N > GATE_MAX_GRID_YZ || cdiv(C, GATE_FWD_CH) > GATE_MAX_GRID_YZ || (size_t)H * W > ((size_t)1 << 30))
+    return fail(MFN_E_UNSUPPORTED, "%s: tensor too large", what);
+  return 0;
+}
+// the 16-byte route: W % 4 == 0 and every pointer given 16-byte aligned (NULL counts as aligned)
+static bool gate_vec4(int W, std::initializer_list<const void *> ptrs) {
+  bool ok = W % 4 == 0;
+  for (const void *q : ptrs) ok = ok && aligned(q, 16);
+  return ok;
+}
+
+int MFN_API(matching_gate_fwd)(const float *raw, const float *mask, const float *tradeoff, int activation, float *out, int N, int C, int H,
+                               int W, void *stream) {
+  if (int rc = gate_dims("matching_gate_fwd", N, C, H, W, activation)) return rc;
+  if (N == 0) return 0;
+  if (!raw || !out) return fail(MFN_E_NULL, "matching_gate_fwd: NULL tensor pointer");
+  const GateFwdParams p{raw, mask, tradeoff, out, N, C, H * W, activation == MFN_ACT_LEAKY_0_1 ? 1 : 0};
+  return hipfail(matching_gate_fwd_launch(p, gate_vec4(W, {raw, mask, tradeoff, out}), (hipStream_t)stream), "matching_gate_fwd");
+}
+
+size_t MFN_API(matching_gate_bwd_workspace_bytes)(int N, int C, int H, int W) {
+  if (N <= 0 || C <= 0 || H <= 0 || W <= 0) return 0;
+  return gate_bwd_ws_bytes(N, C, (size_t)H * W);
+}
+
+int MFN_API(matching_gate_bwd)(const float *gout, const float *gout2, const float *y, const float *raw, const float *mask, int activation,
+                               float *graw, float *gmask, float *gtradeoff, int N, int C, int H, int W, int req_raw, int req_mask,
+                               int req_tradeoff, void *workspace, size_t workspace_bytes, void *stream) {
+  if (int rc = gate_dims("matching_gate_bwd", N, C, H, W, activation)) return rc;
+  if (!req_ok(req_raw) || !req_ok(req_mask) || !req_ok(req_tradeoff))
+    return fail(MFN_E_PARAM, "matching_gate_bwd: every req must be 0 (null), 1 (write) or 3 (add)");
+  if (req_mask && !mask) return fail(MFN_E_PARAM, "matching_gate_bwd: a mask gradient is asked for and no mask is given");
+  if (N == 0 || (!req_raw && !req_mask && !req_tradeoff)) return 0;
+  if (!gout || (activation && !y) || (req_mask && !raw)) return fail(MFN_E_NULL, "matching_gate_bwd: NULL tensor pointer (gout, y, raw)");
+  if ((req_raw && !graw) || (req_mask && !gmask) || (req_tradeoff && !gtradeoff))
+    return fail(MFN_E_NULL, "matching_gate_bwd: NULL gradient pointer with a req that is not null");
+  const GatePlan pl = gate_plan(N, C, (size_t)H * W);
+  const size_t need = req_mask ? gate_bwd_ws_bytes(N, C, (size_t)H * W) : 0;
+  if (need && (!workspace || workspace_bytes < need))
+    return fail(MFN_E_WORKSPACE, "matching_gate_bwd: workspace of %zu bytes needed, %zu given", need, workspace ? workspace_bytes : (size_t)0);
+  if (need && !aligned(workspace, 4)) return fail(MFN_E_ALIGN, "matching_gate_bwd: workspace must be 4-byte aligned");
+  GateBwdParams p{};
+  p.gout = gout; p.gout2 = gout2; p.y = activation ? y : nullptr; p.raw = req_mask ? raw : nullptr; p.mask = mask;
+  p.graw = req_raw ? graw : nullptr; p.gmask = req_mask ? gmask : nullptr; p.gtradeoff = req_tradeoff ? gtradeoff : nullptr;
+  p.partial = need ? (float *)workspace : nullptr;
+  p.N = N; p.C = C; p.HW = H * W; p.leaky = activation == MFN_ACT_LEAKY_0_1 ? 1 : 0; p.cps = pl.cps; p.splits = pl.splits;
+  p.add_raw = req_raw == MFN_REQ_ADD; p.add_mask = req_mask == MFN_REQ_ADD; p.add_tradeoff = req_tradeoff == MFN_REQ_ADD;
+  const bool vec4 = gate_vec4(W, {gout, gout2, p.y, p.raw, mask, p.graw, p.gmask, p.gtradeoff, p.partial});
+  return hipfail(matching_gate_bwd_launch(p, vec4, (hipStream_t)stream), "matching_gate_bwd");
 }
 
 // What conv_bwd_plan decides for mfn_conv2d_bwd and the call executes.  Workspace: [gpre: the gradient before the fused LeakyReLU]

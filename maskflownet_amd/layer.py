@@ -13,6 +13,8 @@ plugs the same C ABI into a real MXNet process.
                                                                     layer.py:32-144
     correlation(im1, im2, md)   the body of MaskFlownet_S.corr / MaskFlownet.corr
                                                                     MaskFlownet.py:193-195, :440-441
+    matching_level(c1, c2, flow, weight, bias, mask, tradeoff, scale, stride, md) -> (corr, warp)
+                                the matching step of one pyramid level, differentiable   MaskFlownet.py:230-236
 """
 import math
 
@@ -105,6 +107,101 @@ class _SharedDeformConvFn(torch.autograd.Function):
             gout, x, flow, ctx.scale, ctx.stride, weight, kernel=kw["kernel"], dilate=kw["dilate"], pad=kw["pad"],
             num_group=kw["num_group"], no_bias=not ctx.has_bias, req=tuple(req))
         return gx, gfl, gw, gb, None, None, None, None
+
+
+class _LeakyCorrelationFn(torch.autograd.Function):
+    """The cost volume with its LeakyReLU(0.1) in the kernel's epilogue (MaskFlownet.py:217), differentiable: backward undoes the
+    activation from the saved output (mfn_leaky_relu_bwd), then mfn_correlation_bwd."""
+
+    @staticmethod
+    def forward(ctx, d1, d2, md):
+        corr = ops.Correlation(d1, d2, kernel_size=1, max_displacement=md, stride1=1, stride2=1, pad_size=md, is_multiply=True,
+                               activation="leaky")
+        ctx.save_for_backward(d1, d2, corr)
+        ctx.md = md
+        return corr
+
+    @staticmethod
+    def backward(ctx, gout):
+        d1, d2, corr = ctx.saved_tensors
+        o = ops.default_ops()
+        g1, g2 = o.Correlation_backward(o.LeakyReLU_backward(gout.contiguous(), corr), d1, d2, kernel_size=1,
+                                        max_displacement=ctx.md, stride1=1, stride2=1, pad_size=ctx.md, is_multiply=True,
+                                        req1="write" if ctx.needs_input_grad[0] else "null",
+                                        req2="write" if ctx.needs_input_grad[1] else "null")
+        return g1, g2, None
+
+
+class _MatchingGateFn(torch.autograd.Function):
+    """MaskFlownet.py:231-233 on the deformable convolution's output: mfn_matching_gate_fwd / _bwd."""
+
+    @staticmethod
+    def forward(ctx, raw, mask, tradeoff, leaky):
+        raw = raw.contiguous()
+        mask = mask.contiguous() if mask is not None else None
+        out = ops.matching_gate(raw, mask, tradeoff.contiguous() if tradeoff is not None else None, leaky=leaky)
+        ctx.save_for_backward(raw, mask, out)
+        ctx.leaky = leaky
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        raw, mask, out = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        req = tuple("write" if n else "null" for n in (need[0], need[1] and mask is not None, need[2]))
+        graw, gmask, gtr = ops.matching_gate_backward(gout.contiguous(), out, raw, mask, leaky=ctx.leaky, req=req)
+        return graw, gmask, gtr, None
+
+
+class _MatchingLevelFn(torch.autograd.Function):
+    """One pyramid level's matching step (MaskFlownet.py:230-236) under autograd, every kernel of both directions the library's:
+    forward  raw = deform(c2, repeat9(flow * scale / stride)); warp = gate(raw, mask, tradeoff); corr = LeakyReLU(Correlation(c1, warp))
+    backward mfn_leaky_relu_bwd -> mfn_correlation_bwd -> mfn_matching_gate_bwd (the cost volume's gradient of warp and the
+             caller's own, either may be absent) -> mfn_deform_conv_shared_bwd.
+    Returns (corr, warp)."""
+
+    @staticmethod
+    def forward(ctx, c1, c2, flow, weight, bias, mask, tradeoff, scale, stride, md, leaky_warp, leaky_corr):
+        o = ops.default_ops()
+        c1, c2, flow = c1.contiguous(), c2.contiguous(), flow.contiguous()
+        mask = mask.contiguous() if mask is not None else None
+        raw = o.deformable_convolution_shared(c2, flow, scale, stride, weight, bias)
+        warp = o.matching_gate(raw, mask, tradeoff.contiguous() if tradeoff is not None else None, leaky=leaky_warp)
+        corr = o.Correlation(c1, warp, kernel_size=1, max_displacement=md, stride1=1, stride2=1, pad_size=md, is_multiply=True,
+                             activation="leaky" if leaky_corr else None)
+        ctx.save_for_backward(c1, c2, flow, weight, raw, warp, corr, mask)
+        ctx.cfg = (float(scale), float(stride), int(md), bool(leaky_warp), bool(leaky_corr), bias is not None)
+        ctx.set_materialize_grads(False)
+        return corr, warp
+
+    @staticmethod
+    def backward(ctx, gcorr, gwarp):
+        c1, c2, flow, weight, raw, warp, corr, mask = ctx.saved_tensors
+        scale, stride, md, leaky_warp, leaky_corr, has_bias = ctx.cfg
+        o = ops.default_ops()
+        need = ctx.needs_input_grad            # c1, c2, flow, weight, bias, mask, tradeoff
+        through_warp = any(need[1:7])
+        g1 = g2 = None
+        if gcorr is not None and (need[0] or through_warp):
+            gc = gcorr.contiguous()
+            if leaky_corr:
+                gc = o.LeakyReLU_backward(gc, corr)
+            g1, g2 = o.Correlation_backward(gc, c1, warp, kernel_size=1, max_displacement=md, stride1=1, stride2=1, pad_size=md,
+                                            is_multiply=True, req1="write" if need[0] else "null",
+                                            req2="write" if through_warp else "null")
+        grads = [g1, None, None, None, None, None, None]
+        ups = [g for g in (gwarp.contiguous() if gwarp is not None else None, g2) if g is not None]
+        if ups and through_warp:
+            need_raw = any(need[1:5])
+            graw, grads[5], grads[6] = o.matching_gate_backward(
+                ups[0], warp, raw, mask, leaky=leaky_warp, out_grad2=ups[1] if len(ups) > 1 else None,
+                req=("write" if need_raw else "null", "write" if (need[5] and mask is not None) else "null",
+                     "write" if need[6] else "null"))
+            if need_raw:
+                req = ["write" if need[i] else "null" for i in (1, 2, 3)] + ["write" if (has_bias and need[4]) else "null"]
+                grads[1:5] = o.deformable_convolution_shared_backward(graw, c2, flow, scale, stride, weight, no_bias=not has_bias,
+                                                                       req=tuple(req))
+        return tuple(grads) + (None,) * 5
 
 
 def _any_grad(*ts):
@@ -241,7 +338,8 @@ class DeformableConv2D(nn.Module):
 
     def forward_matching(self, x, flow, flow_scale, flow_stride, mask=None, tradeoff=None, leaky=True):
         """The warp step of the matching module in one launch (MaskFlownet.py:230-233):
-        LeakyReLU(0.1)(self(x, repeat9(flow*scale/stride)) * sigmoid(mask) + tradeoff).  Inference only."""
+        LeakyReLU(0.1)(self(x, repeat9(flow*scale/stride)) * sigmoid(mask) + tradeoff).  When anything requires a gradient the
+        deformable convolution keeps its output and the gate runs as its own kernel (_MatchingGateFn), both differentiable."""
         if self.weight is None:
             self._materialize(x.shape[1], x.device)
         kw = self._kwargs
@@ -251,13 +349,9 @@ class DeformableConv2D(nn.Module):
             raise ValueError("forward_matching is the reference's warp step (MaskFlownet.py:230-233): no activation between the "
                              "deformable convolution and the gating -- build the block with activation=None")
         if _any_grad(x, flow, mask, tradeoff, self.weight, self.bias):
-            # differentiable form of the same arithmetic (MaskFlownet.py:230-233), elementwise part in torch
-            out = self.forward_shared(x, flow, flow_scale, flow_stride)
-            if mask is not None:
-                out = out * torch.sigmoid(mask)
-            if tradeoff is not None:
-                out = out + tradeoff
-            return torch.nn.functional.leaky_relu(out, 0.1) if leaky else out
+            # the same arithmetic with `raw` kept for the tape: the fused deformable convolution, then the gate's own kernels
+            # (mfn_matching_gate_fwd / _bwd)
+            return _MatchingGateFn.apply(self.forward_shared(x, flow, flow_scale, flow_stride), mask, tradeoff, bool(leaky))
         return ops.default_ops().deformable_matching(x, flow, flow_scale, flow_stride, self.weight, self.bias, mask,
                                                      tradeoff, leaky=leaky, kernel=kw["kernel"], dilate=kw["dilate"],
                                                      pad=kw["pad"], num_group=kw["num_group"], packed=self._packed(x))
@@ -294,6 +388,22 @@ def correlation(im1, im2, md, stride1=1, stride2=1, leaky=False, out=None):
         return torch.nn.functional.leaky_relu(res, 0.1) if leaky else res
     return ops.Correlation(im1, im2, pad_size=md, kernel_size=1, max_displacement=md, stride1=stride1,
                            stride2=stride2, is_multiply=1, activation="leaky" if leaky else None, out=out)
+
+
+def matching_level(c1, c2, flow, weight, bias, mask, tradeoff, scale, stride, md, leaky_warp=True, leaky_corr=True, out=None):
+    """One pyramid level's matching step (MaskFlownet.py:230-236): warp = LeakyReLU(deform(c2, repeat9(flow * scale / stride)) *
+    sigmoid(mask) + tradeoff), corr = LeakyReLU(Correlation(c1, warp, md)) -> (corr, warp); bias, mask, tradeoff may be None.
+    Nothing requires a gradient: the inference form, two launches (deformable_matching, the cost volume with its fused activation).
+    Under autograd: _MatchingLevelFn, the library's kernels in both directions.
+    out: optional destination of corr (see correlation) -- inference only."""
+    if _any_grad(c1, c2, flow, weight, bias, mask, tradeoff):
+        if out is not None:
+            raise RuntimeError("matching_level(out=...) is an inference-time fusion; autograd needs its own output")
+        return _MatchingLevelFn.apply(c1, c2, flow, weight, bias, mask, tradeoff, scale, stride, md, bool(leaky_warp), bool(leaky_corr))
+    warp = ops.default_ops().deformable_matching(c2, flow, scale, stride, weight, bias, mask, tradeoff, leaky=leaky_warp)
+    corr = ops.Correlation(c1, warp, pad_size=md, kernel_size=1, max_displacement=md, stride1=1, stride2=1, is_multiply=1,
+                           activation="leaky" if leaky_corr else None, out=out)
+    return corr, warp
 
 
 class _UpsampleFn(torch.autograd.Function):

@@ -507,7 +507,8 @@ if mx is not None:
 
     # ---- one pyramid level of the matching module in ONE Custom call (MaskFlownet.py:227-236: offsets from the flow, the
     # deformable convolution, [gating by sigmoid(mask) + trade-off], LeakyReLU, cost volume against the other image's features,
-    # LeakyReLU).  Outputs: the cost volume and the warped features (the decoder reads both).  Two launches, one drain -- against
+    # LeakyReLU).  Outputs: the cost volume and the warped features (the decoder reads both).  Forward two launches, one drain;
+    # backward the same level through the gate's own backward kernel (kernels/gate.h), one drain too -- against
     # three Custom calls' worth of host protocol plus the framework's own repeat / expand_dims / reshape kernels that build the
     # 9x-redundant offset tensor.  INTEGRATION.md shows the six lines of MaskFlownet.py it replaces.
     class _MatchingLevel(_Op):
@@ -543,8 +544,61 @@ if mx is not None:
             warp.finish()
 
         def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
-            raise NotImplementedError("mfn_matching_level is the inference form of a pyramid level (--valid / --predict); training "
-                                      "goes through mfn_correlation and mfn_deform_conv, whose backward passes exist")
+            """The level's backward through the raw ABI, one drain: mfn_leaky_relu_bwd -> mfn_correlation_bwd ->
+            mfn_matching_gate_bwd (the cost volume's gradient of warp and out_grad[1], the caller's own) ->
+            mfn_deform_conv_shared_bwd.  The operator is stateless and its outputs stay (corr, warp), so `raw` (the deformable
+            convolution before the gate, which the mask's gradient needs) is recomputed with mfn_deform_conv_shared_fwd into
+            scratch when that gradient is asked for: ONE EXTRA forward convolution per backward call.
+            req per input: data1 = c1, data2 = c2, flow, weight, bias[, mask][, tradeoff]."""
+            rq = [_REQ[r] for r in req]
+            if not any(rq):
+                return
+            c1, c2, flow, w, b = in_data[:5]
+            i_mask = 5 if self.gated else None
+            i_trade = (5 + int(self.gated)) if self.tradeoff else None
+            mask = in_data[i_mask] if self.gated else None
+            r_mask = rq[i_mask] if self.gated else 0
+            r_trade = rq[i_trade] if self.tradeoff else 0
+            conv_side = any(rq[1:5])
+            through_warp = conv_side or r_mask or r_trade
+            corr, warp = out_data[:2]
+            n, c, h, wd = c2.shape
+            cout = w.shape[0]
+            dims = (n, c, h, wd, cout, 3, 3, 1, 1, 1, 1, 1)
+            a = (self.md, 1, 1, 1, self.md, 1)
+            lib = self._begin(c2)
+            # one scratch request BEFORE the first launch (as in forward: growing the buffer between launches would free what an
+            # earlier one is still reading): [forward conv workspace][raw][activated cost-volume gradient][g2][graw][gate][shared bwd]
+            up = lambda v: (v + 255) // 256 * 256
+            feat = up(n * cout * h * wd * 4)
+            sizes = [up(_bytes(lib, "deform_conv_workspace_bytes", n, c, h, wd, cout, 3, 3, 1, 1, 1, 1, 1, 1, 1, 1)) if r_mask else 0,
+                     feat if r_mask else 0,
+                     up(out_grad[0].size * 4) if self.act_corr else 0,
+                     feat if through_warp else 0,
+                     feat if conv_side else 0,
+                     up(_bytes(lib, "matching_gate_bwd_workspace_bytes", n, cout, h, wd)) if r_mask else 0,
+                     up(_bytes(lib, "deform_conv_shared_bwd_workspace_bytes", *dims)) if conv_side else 0]
+            wsp, _ = _workspace(sum(sizes) or 256, c2.context)
+            offs = [sum(sizes[:i]) for i in range(len(sizes))]
+            seg = lambda i: (wsp + offs[i]) if sizes[i] else None
+            if r_mask:         # raw is read for the mask gradient only
+                _check(lib.deform_conv_shared_fwd(_ptr(c2), _ptr(flow), self.scale, self.stride, _ptr(w), _ptr(b), seg(1), *dims,
+                                                  seg(0), sizes[0], None))
+            gcorr = _ptr(out_grad[0])
+            if self.act_corr:
+                _check(lib.leaky_relu_bwd(gcorr, _ptr(corr), seg(2), out_grad[0].size, 0.1, None))
+                gcorr = seg(2)
+            _check(lib.correlation_bwd(gcorr, _ptr(c1), _ptr(warp), _ptr(in_grad[0]) if rq[0] else None, seg(3), n, cout, h, wd, *a,
+                                       rq[0], _REQ["write"] if through_warp else 0, None))
+            if through_warp:
+                _check(lib.matching_gate_bwd(_ptr(out_grad[1]), seg(3), _ptr(warp), seg(1), _ptr(mask), self.act_warp, seg(4),
+                                             _ptr(in_grad[i_mask]) if r_mask else None, _ptr(in_grad[i_trade]) if r_trade else None,
+                                             n, cout, h, wd, _REQ["write"] if conv_side else 0, r_mask, r_trade, seg(5), sizes[5], None))
+            if conv_side:
+                g = [_ptr(in_grad[i]) if rq[i] else None for i in (1, 2, 3, 4)]
+                _check(lib.deform_conv_shared_bwd(seg(4), _ptr(c2), _ptr(flow), self.scale, self.stride, _ptr(w), g[0], g[1], g[2], g[3],
+                                                  *dims, rq[1], rq[2], rq[3], rq[4], seg(6), sizes[6], None))
+            self._end()
 
     @mx.operator.register("mfn_matching_level")
     class _MatchingLevelProp(mx.operator.CustomOpProp):
@@ -578,6 +632,9 @@ if mx is not None:
                 shapes.append((n, cout, h, w))
             d = 2 * self.md + 1
             return shapes, [(n, d * d, h, w), (n, cout, h, w)], []
+
+        def declare_backward_dependency(self, out_grad, in_data, out_data):
+            return list(out_grad) + list(in_data) + list(out_data)
 
         def create_operator(self, ctx, shapes, dtypes):
             return _MatchingLevel(self.scale, self.stride, self.md, self.gated, self.tradeoff, self.act_warp, self.act_corr)

@@ -1154,6 +1154,78 @@ class OpSet:
             Cout, kh, kw, ph, pw, dh, dw, num_group, self.ad.ptr(ws), self.ad.nbytes(ws), self.ad.stream(x)))
         return out
 
+    def _gate_args(self, what, raw, mask, shape=None):
+        """(N, C, H, W) of the gate's tensors; mask must be (N,1,H,W)."""
+        if self.ad.ndim(raw) != 4 or (shape is not None and self.ad.shape(raw) != shape):
+            raise ValueError("%s: raw must be 4-D%s, got %s" % (what, "" if shape is None else " %s" % (shape,), self.ad.shape(raw)))
+        N, C, H, W = self.ad.shape(raw)
+        if mask is not None and self.ad.shape(mask) != (N, 1, H, W):
+            raise ValueError("%s: mask must be %s" % (what, (N, 1, H, W)))
+        return N, C, H, W
+
+    def matching_gate(self, raw, mask=None, tradeoff=None, leaky=True, out=None):
+        """MaskFlownet.py:231-233 on the deformable convolution's output: LeakyReLU(0.1)(raw * sigmoid(mask) + tradeoff); mask
+        (N,1,H,W), tradeoff (N,C,H,W), both optional -- the training form of deformable_matching's epilogue (mfn_matching_gate_fwd),
+        which keeps `raw` for the backward pass."""
+        (r,) = self._in(raw)
+        m = self._in(mask)[0] if mask is not None else None
+        tr = self._in(tradeoff)[0] if tradeoff is not None else None
+        N, C, H, W = self._gate_args("matching_gate", r, m)
+        if tr is not None and self.ad.shape(tr) != (N, C, H, W):
+            raise ValueError("matching_gate: tradeoff must be %s" % ((N, C, H, W),))
+        out = self._out(out, r, (N, C, H, W), "matching_gate")
+        p = lambda a: self.ad.ptr(a) if a is not None else None
+        self.check(self.ns.matching_gate_fwd(self.ad.ptr(r), p(m), p(tr), 1 if leaky else 0, self.ad.ptr(out), N, C, H, W,
+                                             self.ad.stream(r)))
+        return out
+
+    def matching_gate_backward(self, out_grad, output, raw, mask=None, leaky=True, out_grad2=None,
+                               req=("write", "write", "write"), out=None):
+        """Gradients of matching_gate w.r.t. (raw, mask, tradeoff) from the forward OUTPUT (mfn_matching_gate_bwd); out_grad2: a
+        second upstream gradient, added to out_grad first.  The mask gradient's channel sum is added in a fixed order: the same
+        bits on every call.  `raw` may be None when no mask gradient is asked for.  out: optional (graw, gmask, gtradeoff)
+        buffers (required for req "add")."""
+        what = "matching_gate_backward"
+        go, y = self._in(out_grad, output)
+        go2 = self._in(out_grad2)[0] if out_grad2 is not None else None
+        m = self._in(mask)[0] if mask is not None else None
+        r = self._in(raw)[0] if raw is not None else None
+        N, C, H, W = self._gate_args(what, go, m)
+        for name, a in (("output", y), ("raw", r), ("out_grad2", go2)):
+            if a is not None and self.ad.shape(a) != (N, C, H, W):
+                raise ValueError("%s: %s has shape %s, expected %s" % (what, name, self.ad.shape(a), (N, C, H, W)))
+        rq = [_REQ[v] for v in req]
+        if len(rq) != 3:
+            raise ValueError("%s: req must be (raw, mask, tradeoff)" % what)
+        if m is None:
+            rq[1] = 0
+        elif rq[1] and r is None:
+            raise ValueError("%s: the mask gradient needs raw" % what)
+        want = ((N, C, H, W), (N, 1, H, W), (N, C, H, W))
+        given = tuple(out) if out is not None else (None, None, None)
+        if len(given) != 3:
+            raise ValueError("%s: out must be (graw, gmask, gtradeoff)" % what)
+        grads = []
+        for i, (g, shp) in enumerate(zip(given, want)):
+            if not rq[i]:
+                grads.append(None)
+            elif g is None:
+                if rq[i] == _REQ["add"]:
+                    raise ValueError("%s: req 'add' needs the buffer to add into (out[%d])" % (what, i))
+                grads.append(self.ad.empty(go, shp))
+            else:
+                self.ad.require_destination(g, go, what)   # written in place: no silent copy
+                if self.ad.shape(g) != shp:
+                    raise ValueError("%s: out[%d] has shape %s, expected %s" % (what, i, self.ad.shape(g), shp))
+                grads.append(g)
+        p = lambda a: self.ad.ptr(a) if a is not None else None
+        nbytes = self.ns.matching_gate_bwd_workspace_bytes(N, C, H, W) if rq[1] else 0
+        ws = self._workspace(go, nbytes) if nbytes else None
+        self.check(self.ns.matching_gate_bwd(self.ad.ptr(go), p(go2), self.ad.ptr(y), p(r), p(m), 1 if leaky else 0, p(grads[0]),
+                                             p(grads[1]), p(grads[2]), N, C, H, W, rq[0], rq[1], rq[2], p(ws),
+                                             self.ad.nbytes(ws) if ws is not None else 0, self.ad.stream(go)))
+        return tuple(grads)
+
     # ---- Convolution / Deconvolution (SURVEY.md 8 f-4b: nn.Conv2D / nn.Conv2DTranspose of MaskFlownet.py:79-163) ----
     def conv_out_shape(self, H, W, kernel, stride=(1, 1), pad=(0, 0), dilate=(1, 1), transposed=False, adj=(0, 0)):
         (kh, kw), (sh, sw), (ph, pw), (dh, dw), (ah, aw) = map(self._pair, (kernel, stride, pad, dilate, adj))
@@ -1433,6 +1505,14 @@ def warp(*a, **k):
 
 def deformable_convolution_shared(*a, **k):
     return default_ops().deformable_convolution_shared(*a, **k)
+
+
+def matching_gate(*a, **k):
+    return default_ops().matching_gate(*a, **k)
+
+
+def matching_gate_backward(*a, **k):
+    return default_ops().matching_gate_backward(*a, **k)
 
 
 def offsets_from_flow(*a, **k):

@@ -8,8 +8,12 @@ what the tape calls is the library:
 * convolutions / transposed convolutions with their fused LeakyReLU: `mfn_conv2d_fwd` / `mfn_conv2d_bwd` (`_ConvFn`),
 * cost volumes, the deformable matching step, `Upsample`: the autograd functions of `layer.py`
   (`mfn_correlation_fwd/_bwd`, `mfn_deform_conv_shared_fwd/_bwd`, `mfn_upsample_fwd/_bwd`),
-* concatenation, the gating `warp * sigmoid(mask) + tradeoff`, the loss arithmetic: torch element-wise glue, as the
-  reference's are MXNet's.
+* concatenation and the composed loss's arithmetic: torch element-wise glue, as the reference's are MXNet's.  So is, by default,
+  the gating `warp * sigmoid(mask) + tradeoff` with its LeakyReLU; `LibraryBackend(fused_matching=True)` runs a level's whole
+  matching step -- deformable convolution, gate, cost volume and its activation -- as one autograd function on the library
+  (`layer.matching_level`: `mfn_matching_gate_fwd/_bwd` between the kernels above) and keeps the LeakyReLU of the cost volumes
+  that stand alone in their epilogue: no torch leaky_relu kernel is left in a step, and of torch's sigmoid only the occlusion
+  masks the networks hand out (`MaskFlownet.py:303-305`, `:309`), which are no part of a matching step.
 
 `network.MaskFlownetS` is the inference form of the same graph (pre-allocated concat buffers, packed weights, one
 hipGraph); the parameter names are shared (`network.random_params`, the reference checkpoint's keys).
@@ -59,10 +63,17 @@ class _ConvFn(torch.autograd.Function):
 
 class LibraryBackend:
     """The differentiable layer set of the network, every member's forward AND backward a libmfn_hip.so call.  (The tests pass
-    a pure-torch implementation of the same four members to check the gradients of the composition.)"""
+    a pure-torch implementation of the same four members to check the gradients of the composition.)
+    fused_matching=True (opt-in; the default waits for the measurement cited in DESIGN.md 4.4): the backend also has
+    matching_level -- a pyramid level's matching step as one differentiable call, layer.matching_level --, which the networks
+    use where a backend offers it, and its correlation keeps the LeakyReLU in the kernel's epilogue under autograd too."""
 
-    def __init__(self):
+    def __init__(self, fused_matching=False):
         self._up = {}
+        self.fused_matching = bool(fused_matching)
+        if self.fused_matching:      # members of the instance: a backend without the flag has none of them
+            self.matching_level = self._matching_level
+            self.correlation = self._leaky_correlation
 
     def conv(self, x, w, b, stride=1, dilation=1, act=True, transposed=False):
         return _ConvFn.apply(x, w, b, stride, dilation, act, transposed)
@@ -73,6 +84,15 @@ class LibraryBackend:
     def deform(self, x, flow, w, b, scale, stride):   # MaskFlownet.py:230: deform(x, repeat9(flow * scale / stride))
         return layer._SharedDeformConvFn.apply(x.contiguous(), flow.contiguous(), w, b, scale, stride,
                                                {"kernel": (3, 3), "dilate": (1, 1), "pad": (1, 1), "num_group": 1}, None)
+
+    def _matching_level(self, c1, c2, flow, w, b, scale, stride, md, mask=None, tradeoff=None):
+        """MaskFlownet.py:230-236 (gated) / :460-463 (the cascade: the LeakyReLU alone) -> (corr, warp)."""
+        return layer.matching_level(c1, c2, flow, w, b, mask, tradeoff, scale, stride, md)
+
+    def _leaky_correlation(self, a, b, md):
+        if layer._any_grad(a, b):
+            return layer._LeakyCorrelationFn.apply(a.contiguous(), b.contiguous(), md)
+        return layer.correlation(a.contiguous(), b.contiguous(), md, leaky=True)
 
     def upsample(self, x, factor):
         if factor not in self._up:
@@ -120,6 +140,7 @@ class MaskFlownetSTrainable(nn.Module):
             c[l] = x
         preds, flows = [], {}
         flow = mask = feat = None
+        level = getattr(self.B, "matching_level", None)      # LibraryBackend(fused_matching=True): the matching step in one call
         for l in (6, 5, 4, 3, 2):
             c1, c2 = c[l][:N], c[l][N:]
             if l == 6:
@@ -129,9 +150,12 @@ class MaskFlownetSTrainable(nn.Module):
                 trade = self.conv("conv%df" % l, feat, act=False)
                 w, b = self._p("deform%d" % l)
                 # MaskFlownet.py:230-233: deform(c2, repeat9(flow * scale / stride)) * sigmoid(mask) + tradeoff, LeakyReLU
-                warp = self.B.deform(c2, flow_up, w, b, SCALE, float(STRIDES[l]))
-                warp = torch.nn.functional.leaky_relu(warp * torch.sigmoid(mask_up) + trade, 0.1)
-                corr = self.B.correlation(c1, warp, MD)
+                if level is not None:
+                    corr, _ = level(c1, c2, flow_up, w, b, SCALE, float(STRIDES[l]), MD, mask=mask_up, tradeoff=trade)
+                else:
+                    warp = self.B.deform(c2, flow_up, w, b, SCALE, float(STRIDES[l]))
+                    warp = torch.nn.functional.leaky_relu(warp * torch.sigmoid(mask_up) + trade, 0.1)
+                    corr = self.B.correlation(c1, warp, MD)
                 x = torch.cat([corr, c1, feat, flow_up], 1)
             for k in range(len(DECODER)):            # x = concat(conv(x), x)
                 x = torch.cat([self.conv("conv%d_%d" % (l, k), x), x], 1)
@@ -190,14 +214,18 @@ class MaskFlownetTrainable(nn.Module):
             d[l] = x
         preds = []
         flow = feat = None
+        level = getattr(self.B, "matching_level", None)
         for l in (6, 5, 4, 3, 2):
             c1 = h["c"][l][:N]
             c2 = c1 if l in (2, 3) else h["c"][l][N:]          # c2s = [c21, c12, c13, c24, c25, c26] (:307)
             c3, c4 = d[l][:N], d[l][N:]
             flow_in = h["flows"][6] if l == 6 else self.B.upsample(flow, 2)                              # :457
             w, b = self.P[_key("deform%d.weight" % l)], self.P[_key("deform%d.bias" % l)]
-            warp = torch.nn.functional.leaky_relu(self.B.deform(c2, flow_in, w, b, SCALE, float(STRIDES[l])), 0.1)   # :460-461
-            cu = self.B.correlation(c1, warp, MD_CASCADE)
+            if level is not None:                # no mask, no trade-off: the gate is the LeakyReLU alone
+                cu, _ = level(c1, c2, flow_in, w, b, SCALE, float(STRIDES[l]), MD_CASCADE)
+            else:
+                warp = torch.nn.functional.leaky_relu(self.B.deform(c2, flow_in, w, b, SCALE, float(STRIDES[l])), 0.1)   # :460-461
+                cu = self.B.correlation(c1, warp, MD_CASCADE)
             cv = self.B.correlation(c3, c4, MD_CASCADE)
             x = torch.cat([cu, cv, flow_in], 1) if l == 6 else torch.cat([c1, feat, cu, cv, flow_in, h["flows"][l]], 1)   # :466, :480
             for k in range(len(DECODER)):
