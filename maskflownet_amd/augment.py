@@ -118,6 +118,13 @@ class GeometryAugmentation:
     def table(self, d=None):
         return geometry_table(self.draw() if d is None else d, self._orig_shape, self._target_shape)
 
+    def state(self):
+        """What the next call's draws depend on (picklable): the numpy bit generator's state.  set_state() continues from it."""
+        return {"rng": self.rng.bit_generator.state}
+
+    def set_state(self, state):
+        self.rng.bit_generator.state = state["rng"]
+
     def __call__(self, img1, img2, flow, mask, label_order=0, out=None):
         from . import ops
         if tuple(img1.shape) != (self._batch_size, 3) + self._orig_shape:
@@ -192,6 +199,15 @@ class ColorAugmentation:
 
     def table(self, d):
         return color_table(d, self._eigen_aug)
+
+    def state(self):
+        """What the next call's draws and noise depend on (picklable): the numpy bit generator's state, the Philox key and the call
+        counter.  set_state() continues from it."""
+        return {"rng": self.rng.bit_generator.state, "seed": int(self.seed), "calls": int(self.calls)}
+
+    def set_state(self, state):
+        self.rng.bit_generator.state = state["rng"]
+        self.seed, self.calls = int(state["seed"]), int(state["calls"])
 
     def __call__(self, img1, img2, out=None):
         from . import ops

@@ -564,6 +564,27 @@ def load_checkpoint(prefix, net, trainer=None):
         trainer.load_states(prefix + ".states")
 
 
+def load_head(path, net):
+    """MaskFlownet.load_head (MaskFlownet.py:410-411, main.py:133): a MaskFlownet_S checkpoint -- `path` is its .params file -- into the
+    frozen head of a MaskFlownetTrainable, in place; the cascade keeps what it has.  Refuses missing names, unexpected names and wrong
+    shapes before it changes anything."""
+    from . import io
+    if not isinstance(net, MaskFlownetTrainable):
+        raise TypeError("load_head: a MaskFlownetTrainable is expected, got %r" % type(net))
+    got = io.load_params(path)
+    own = reference_named_parameters(net.head)
+    missing = [k for k, _ in own if k not in got]
+    unexpected = [k for k in got if k not in {k for k, _ in own}]
+    if missing or unexpected:
+        raise KeyError("load_head: %s lacks %s and has %s without a parameter in the head" % (path, missing, unexpected))
+    for k, p in own:
+        if tuple(got[k].shape) != tuple(p.shape):
+            raise ValueError("load_head: %s has shape %s, the parameter %s" % (k, got[k].shape, tuple(p.shape)))
+    with torch.no_grad():
+        for k, p in own:
+            p.copy_(torch.from_numpy(np.ascontiguousarray(got[k])))
+
+
 def train_step(net, loss_fn, opt, im1, im2, label, mask, buckets=None, global_batch=None):
     """pipeline.py:95-114: forward, loss, `loss.backward()` (the per-sample losses summed), the gradient exchange, and
     `trainer.step(batch_size)` -- the optimizer sees (sum over the GLOBAL batch of the per-sample gradients) / global_batch.
